@@ -11,7 +11,8 @@ gathered to rank 0 by the product's C-ABI gather (rt_gather_frame: ncclGather ov
 the field "gather" names it; the one-GPU gloo rehearsal uses torch.distributed.gather). Scene upload, RCCL init and the
 op-count pass are outside the timed region. value = W*H*spp_eff*steps / max-over-ranks time.
 
-Also reported (one JSON line on rank 0):
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print the
+result line (one JSON line on rank 0). With --full the line also carries:
   roofline     FP64 VALU roofline of rt_trace: counted algorithmic flops per launch / the
                kernel's average duration (HIP events recorded by the library around each
                rt_trace launch on the bench stream, rt_scene_trace_ms), vs 78.6 TF; render_ms =
@@ -24,7 +25,12 @@ Also reported (one JSON line on rank 0):
                built here) on this host's cores, timed on a bounded stratum subset of the same
                frame (rank 0, N = 1 only).
 
+--dump-outputs DIR writes what the last timed step returned to its caller, the gathered frame
+(rank 0's [H, W, 3] float32 sums over the samples), as DIR/frame.npy. The scene, camera and seed
+are fixed by the arguments, so two builds given the same arguments can be compared pixel for pixel.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--width 800] [--spp 1000]
+                       [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 At --gpus N > 1 without torchrun (WORLD_SIZE unset) the script starts its N ranks itself
 (self_launch: one child process per GPU, torchrun's environment, rank 0's line relayed).
@@ -60,7 +66,12 @@ SCALING_PROJECTION = {("BASELINE configs[1]", 2): 0.983, ("BASELINE configs[1]",
                       ("BASELINE configs[1]", 8): 0.939}
 
 
-def parse():
+# --dump-outputs writes at most this much; a larger frame is written as a fixed sample of pixels
+DUMP_MAX_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20240229
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -72,13 +83,22 @@ def parse():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame to DIR/frame.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report what the headline figure does not need: the "
+                         "op-count pass and the roofline / hbm blocks, and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target CPU-baseline work (bounded sample)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-count", action="store_true", help="skip the op-count pass")
+                    help="with --full: target CPU-baseline work (bounded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-count", action="store_true",
+                    help="with --full: skip the op-count pass (and the roofline / hbm blocks)")
     ap.add_argument("--launch-check", action="store_true",
                     help="check the N-rank launch over gloo without a GPU (no render)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     c = CONFIGS[a.config]
     for k in ("scene", "width", "spp", "depth"):
         if getattr(a, k) is None:
@@ -243,11 +263,29 @@ def launch_check(args):
     dist.destroy_process_group()
 
 
-def main():
-    args = parse()
+def dump_outputs(directory, frame):
+    """--dump-outputs: the frame the last timed step returned ([H, W, 3] float32, on the device
+    or the host) as DIR/frame.npy. A frame above DUMP_MAX_BYTES (C5) is written as a fixed,
+    seeded sample of its pixels, in image order: frame.npy is then [K, 3]."""
+    import numpy as np
+
+    out = frame.detach().cpu().numpy().astype(np.float32, copy=False)
+    if out.nbytes > DUMP_MAX_BYTES:
+        px = out.reshape(-1, out.shape[-1])
+        k = DUMP_MAX_BYTES // (px.shape[1] * px.itemsize)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], k, replace=False))
+        out = px[idx]
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "frame.npy", np.ascontiguousarray(out))
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the driver's plain `python3 bench.py --gpus N`: become the launcher of N ranks
-        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
+        raise SystemExit(self_launch(args.gpus, argv))
     if args.launch_check:
         return launch_check(args)
     import torch
@@ -320,18 +358,19 @@ def main():
             ev[2].record(stream)  # the gather has completed on this stream
         return out
 
-    # ---- op counts for the roofline (outside the timed region; deterministic)
+    # ---- --full: op counts for the roofline (outside the timed region; deterministic)
     ops = None
-    if not args.no_count:
+    if args.full and not args.no_count:
         copts = rt.make_opts(cam, seed=args.seed, row_begin=b, row_step=s, n_rows=n,
                              flags=rt.RT_FLAG_OVERWRITE | rt.RT_FLAG_COUNT_OPS, device=local)
         st = ds.render_device(cam, copts, local_buf.data_ptr(), stream.cuda_stream, stats=True)
         ops = st.op_counts()
 
-    # one product render with stats (outside the timed region): the bytes the path kernel
-    # stores per launch (f64 segment partials + tail samples: its workspace)
-    pst = ds.render_device(cam, opts, local_buf.data_ptr(), stream.cuda_stream, stats=True)
-    out_bytes_launch = pst.out_bytes / max(1, pst.launches)
+    # --full: one product render with stats (outside the timed region): the bytes the path
+    # kernel stores per launch (f64 segment partials + tail samples: its workspace)
+    if args.full:
+        pst = ds.render_device(cam, opts, local_buf.data_ptr(), stream.cuda_stream, stats=True)
+        out_bytes_launch = pst.out_bytes / max(1, pst.launches)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -465,10 +504,12 @@ def main():
                     "note": "measured PMC bytes (profile above) / this run's rt_trace time; the "
                             "kernel is FP64-VALU bound, HBM is not its roof",
                 }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(blob, cam, args.seed, args.cpu_seconds)
             res["speedup_vs_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
         assert frame is not None and frame.shape == (H, W, 3)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
         print(json.dumps(res), flush=True)
     ds.close()
     if rccl is not None:
