@@ -3,6 +3,7 @@
 #   build/librthost.so     C++ scene builder + output stage (include/rt_host.h)
 #   build/rt_render_cli    main.rs-equivalent host program (preset -> PPM)
 #   build/librtgather.so   RCCL framebuffer gather for one process per GPU (include/rt_gather.h)
+#   build/rng_key_check    host check of the split stream key (rt_rng.h)
 #   oracle/_build/*.so     CPU restatement (test infrastructure only)
 PKG      := surely-raytracing_amd
 CSRC     := $(PKG)/csrc
@@ -19,13 +20,14 @@ DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(C
 DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
-.PHONY: all device host oracle cli gather clean
-all: device host oracle cli gather
+.PHONY: all device host oracle cli gather checks clean
+all: device host oracle cli gather checks
 
 device: $(BUILD)/librtmi355x.so
 host: $(BUILD)/librthost.so
 cli: $(BUILD)/rt_render_cli
 gather: $(BUILD)/librtgather.so
+checks: $(BUILD)/rng_key_check
 oracle: oracle/_build/liboracle_f32.so oracle/_build/liboracle_f64.so oracle/_build/liboracle_f64fma.so
 
 # device headers embedded for the scene-specialised kernels compiled at run time (rt_jit.cpp)
@@ -58,6 +60,11 @@ $(BUILD)/librthost.so: $(HOST_SRC) $(CSRC)/host/scene.hpp include/rt_host.h incl
 
 $(BUILD)/rt_render_cli: $(CSRC)/host/rt_render_cli.cpp $(BUILD)/librthost.so $(BUILD)/librtmi355x.so
 	g++ $(CXXFLAGS) $< -o $@ -L$(BUILD) -lrthost -lrtmi355x -Wl,-rpath,'$$ORIGIN'
+
+# host check of the split stream key against rng_seed (tests/test_rng_key.py runs it)
+$(BUILD)/rng_key_check: $(CSRC)/host/rng_key_check.cpp $(CSRC)/rt_rng.h
+	@mkdir -p $(BUILD)
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall $< -o $@
 
 oracle/_build/liboracle_f32.so: oracle/rt_oracle.c include/rt_mi355x.h
 	@mkdir -p oracle/_build

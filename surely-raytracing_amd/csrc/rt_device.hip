@@ -231,8 +231,9 @@ LdsPlan plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32_t flags, b
   const bool bvh = hdr.has_bvh != 0;
   L.block = bvh ? kBlockBvh : kBlock;
   // static LDS of the path kernel: the per-lane f64 running sums (trace_body sh_acc; non-BVH
-  // kernels also the row totals sh_row and the bounce's throughput factor and ending radiance,
-  // sh_f / sh_le), the op counters, slack for the profiling build
+  // kernels also the row totals sh_row, the bounce's throughput factor and ending radiance,
+  // sh_f / sh_le, and the item's stream key sh_key: 80 of the 96 bytes per lane), the op
+  // counters, slack for the profiling build
   L.static_lds = (size_t)L.block * (bvh ? 24 : 96) + 512 + (count ? 128 : 0);
 #ifdef RT_PROF
   L.static_lds += 4096;  // the profiling build's counters (tools_gpu/prof_*.py)

@@ -208,6 +208,7 @@ struct Emitter {
   uint32_t max_chain = 0;
   bool has_bvh = false, has_volume = false, volume_in_bvh = false, all_sphere_volumes = true;
   bool nested_volumes = false;
+  bool has_moving = false;  // a sphere record with RTL_SPHERE_MOVING was emitted
   int bvh_depth = 0;  // BVH subtrees enclosing the record being emitted
   size_t last_exit_end = (size_t)-1;  // end position of the most recent EXIT node
   size_t last_skip_target = (size_t)-1;
@@ -330,7 +331,7 @@ struct Emitter {
     size_t p = push(RTL_SPHERE, RTL_SPHERE_WORDS);
     const double* f = n.f;  // c 0-2, radius 3, cvec 4-6
     w[p + 2] = (uint32_t)(n.mat < 0 ? 0 : n.mat);
-    if (n.moving) w[p] |= RTL_SPHERE_MOVING;
+    if (n.moving) w[p] |= RTL_SPHERE_MOVING, has_moving = true;
     putd(w, p, 0, f[0]), putd(w, p, 1, f[1]), putd(w, p, 2, f[2]), putd(w, p, 3, f[3]);
     putd(w, p, 4, f[4]), putd(w, p, 5, f[5]), putd(w, p, 6, f[6]);
     putd(w, p, 7, 1.0 / f[3]);  // IEEE 1/r: outward = (p - c) / r by one residual step (rt_kernel.h)
@@ -838,6 +839,7 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
       *err = le.err;
       return le.status;
     }
+    F.has_moving |= le.has_moving;
     if (is_list && n_lights == 0) {
       // An empty HittableList light object panics in the reference exactly like render_par.
       is_list = 0;
@@ -868,6 +870,7 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
   h.pdf_materials = pdf_mats;
   h.has_textures = textured;
   h.has_isotropic = isotropic;
+  F.has_moving |= em.has_moving;
   return RT_OK;
 }
 

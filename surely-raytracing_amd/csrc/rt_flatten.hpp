@@ -19,6 +19,7 @@ struct FlatScene {
   std::vector<uint32_t> lights;       // node-format light records
   std::vector<uint32_t> light_offs;   // word offset of each light record
   std::vector<uint8_t> texels;
+  bool has_moving = false;            // a sphere record (world or lights) carries RTL_SPHERE_MOVING
 };
 
 // Conservative bounds of a leaf record (QUAD, QUADS batch, SPHERE), by record word position.

@@ -557,7 +557,9 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
   if (any && *any && *any != '0') sc = RTL_SC_ANY;
   char scb[64];
   std::snprintf(scb, sizeof scb, "  static constexpr uint32_t kScene = 0x%xu;\n", sc);
-  o << scb << "};\n";
+  // a ray's time is read by moving spheres only (object.rs:107-112): without one the path kernel
+  // keeps no time across the bounces
+  o << scb << "  static constexpr bool kMoving = " << (F.has_moving || sc == RTL_SC_ANY ? "true" : "false") << ";\n};\n";
   return pre.str() + o.str();
 }
 

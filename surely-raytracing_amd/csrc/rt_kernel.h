@@ -2034,6 +2034,7 @@ constexpr uint32_t kScMetal = RTL_SC_METAL, kScDielectric = RTL_SC_DIELECTRIC,
 template <int VN>
 struct TravInterpN {
   static constexpr uint32_t kScene = kScAny;
+  static constexpr bool kMoving = true;  // the scene may hold moving spheres (a ray's time is read)
   template <bool COUNT, bool VOL, bool BVH, bool VOLB, bool VOLI>
   static __device__ __forceinline__ bool world(const TraceParams& P, d3& ro, d3& rd, double tm,
                                                double& t, uint32_t& hn, int& hf, Rng& g,
@@ -2180,6 +2181,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool LDSF = !BVH;
   __shared__ wt sh_f[LDSF ? 3 * NB : 1];
   __shared__ wt sh_le[LDSF ? 3 * NB : 1];
+  // Non-BVH kernels: the first round of the item's stream key (rt_rng.h), its pixel term and the
+  // sample term of the item's next sample, formed at the claim; a camera ray then costs one add
+  // and the hash's two remaining rounds instead of the pixel and sample indices and the round
+  // (BVH kernels: no LDS to spare for the slot, they hash the indices per sample)
+  constexpr bool SPLITKEY = !BVH;
+  __shared__ uint32_t sh_key[SPLITKEY ? 2 * NB : 1];
   const int tid = threadIdx.x;
 
   d3 ro = mk(0., 0., 0.), rd = ro;
@@ -2299,6 +2306,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         sij = (rowp ? 0x80000000u : 0u) | (uint32_t)s_jp << 16 | (uint32_t)s_i;
         oslot = obase + (tailp ? (uint32_t)s_i * 64u : 0u) + (uint32_t)pv;
         sh_acc[tid] = 0.0, sh_acc[NB + tid] = 0.0, sh_acc[2 * NB + tid] = 0.0;
+        if constexpr (SPLITKEY) {
+          const kparams_t Q = kparams();
+          const int y = Q->row_begin + kr * Q->row_step;
+          sh_key[tid] = rng_key_pixel(Q->seed_lo, (uint32_t)(y * Q->W + x));
+          sh_key[NB + tid] =
+              rng_key_sample(Q->seed_lo, Q->seed_hi, (uint32_t)(s_jp * Q->sqrt_spp + s_i));
+        }
         fresh = true;
       }
     }
@@ -2327,8 +2341,14 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const int y = Q->row_begin + (int)((xk >> 16) & 0x7fffu) * Q->row_step;
       const int s_i = (int)(sij & 0xffffu), s_j = (int)((sij >> 16) & 0x7fffu);
       // get_ray render.rs:218-249 (stratum (s_i, s_j): 2 jitter draws, defocus disk, time)
-      g = rng_seed(Q->seed_lo, Q->seed_hi, (uint32_t)(y * Q->W + x),
-                   (uint32_t)(s_j * Q->sqrt_spp + s_i));
+      if constexpr (SPLITKEY) {  // an item's samples are consecutive: the sample term moves on by one
+        const uint32_t v1 = sh_key[NB + tid];
+        g = rng_key_mix(sh_key[tid], v1);
+        sh_key[NB + tid] = rng_key_next(v1);
+      } else {
+        g = rng_seed(Q->seed_lo, Q->seed_hi, (uint32_t)(y * Q->W + x),
+                     (uint32_t)(s_j * Q->sqrt_spp + s_i));
+      }
       C.inc(RT_OP_SAMPLES);
       d3 pc = vfma((double)y, karr3(Q->dv), vfma((double)x, karr3(Q->du), karr3(Q->p00)));
       double px = fma(Q->rs, (double)s_i + rnd(g), -0.5);
@@ -2348,7 +2368,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       }
       ro = origin;
       rd = ps - origin;
-      tm = rnd(g);
+      // the ray's time (render.rs:246): read by moving spheres only; a scene without one takes
+      // the draw (the stream moves on as the reference's) and keeps no time across the bounces
+      if constexpr (Trav::kMoving) {
+        tm = rnd(g);
+      } else {
+        (void)rng_u32(g);
+      }
       beta = mkw(1, 1, 1);
       depth = Q->max_depth;  // RT_XS_* cleared
       alive = true;
@@ -2463,7 +2489,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       }
     } else if (type == RTL_SPHERE) {
       d3 c = ld3(X, 0);
-      if (X[0] & RTL_SPHERE_MOVING) c = vfma(tm, ld3(X, 4), c);
+      if (Trav::kMoving && (X[0] & RTL_SPHERE_MOVING)) c = vfma(tm, ld3(X, 4), c);
       // (p - c) / radius (object.rs:169): q = x (1/r) with the host's IEEE reciprocal, then one
       // residual step q + fma(-q, r, x) (1/r), which is the correctly rounded quotient
       // (Markstein: 1/r correctly rounded, q within an ulp), i.e. the reference's division

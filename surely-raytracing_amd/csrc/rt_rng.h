@@ -26,8 +26,40 @@ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int k) { return (x << k) 
 // distinct states. The seed words are wave-uniform (scalar ALU); per lane the hash costs six
 // v_mul_lo_u32 where round 5's pcg4d of (pixel, sample, seed_lo, seed_hi) cost ten, and the
 // camera-ray block that seeds runs in nearly every bounce iteration of a wave.
-__device__ __forceinline__ Rng rng_seed(uint32_t seed_lo, uint32_t seed_hi, uint32_t pixel,
-                                        uint32_t sample) {
+//
+// The split form (rng_key_pixel, rng_key_sample, rng_key_next, rng_key_mix) is the same hash with
+// its first round taken apart: the pixel term and the sample term are formed once per pool item,
+// and inside an item, whose samples are consecutive, the sample term advances by one add (exact in
+// 32-bit modular arithmetic). rng_key_mix(rng_key_pixel(lo, p), rng_key_sample(lo, hi, s)) ==
+// rng_seed(lo, hi, p, s) for every argument (csrc/host/rng_key_check.cpp compares them).
+__host__ __device__ __forceinline__ uint32_t rng_key_pixel(uint32_t seed_lo, uint32_t pixel) {
+  const uint32_t k0 = (seed_lo ^ 0x85EBCA6Bu) * 0x9E3779B9u + 1013904223u;
+  return pixel * 1664525u + k0;
+}
+__host__ __device__ __forceinline__ uint32_t rng_key_sample(uint32_t seed_lo, uint32_t seed_hi,
+                                                            uint32_t sample) {
+  const uint32_t k0 = (seed_lo ^ 0x85EBCA6Bu) * 0x9E3779B9u + 1013904223u;
+  const uint32_t k1 = (seed_hi ^ 0xC2B2AE35u) * 0x9E3779B9u + (k0 ^ 0x27D4EB2Fu);
+  return sample * 1664525u + k1;
+}
+// the sample term of sample + 1
+__host__ __device__ __forceinline__ uint32_t rng_key_next(uint32_t sample_term) {
+  return sample_term + 1664525u;
+}
+__host__ __device__ __forceinline__ Rng rng_key_mix(uint32_t v0, uint32_t v1) {
+  v0 += v1 * 1664525u;
+  v1 += v0 * 1664525u;
+  v0 ^= v0 >> 16;
+  v1 ^= v1 >> 16;
+  v0 += v1 * 1664525u;
+  v1 += v0 * 1664525u;
+  v0 ^= v0 >> 16;
+  v1 ^= v1 >> 16;
+  if ((v0 | v1) == 0u) v0 = 0x9E3779B9u;  // xoroshiro64*'s state must not be all zero
+  return {v0, v1};
+}
+__host__ __device__ __forceinline__ Rng rng_seed(uint32_t seed_lo, uint32_t seed_hi,
+                                                 uint32_t pixel, uint32_t sample) {
   const uint32_t k0 = (seed_lo ^ 0x85EBCA6Bu) * 0x9E3779B9u + 1013904223u;
   const uint32_t k1 = (seed_hi ^ 0xC2B2AE35u) * 0x9E3779B9u + (k0 ^ 0x27D4EB2Fu);
   uint32_t v0 = pixel * 1664525u + k0, v1 = sample * 1664525u + k1;
