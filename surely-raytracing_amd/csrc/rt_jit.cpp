@@ -118,8 +118,77 @@ std::string lit3(double x, double y, double z) {
   return "mk(" + lit(x) + ", " + lit(y) + ", " + lit(z) + ")";
 }
 
+// Deferred light-list PDF (rt_kernel.h trace_body DEFER): a bounce's scattered ray (p, dir) is the
+// next world query's ray bit for bit, so when every top-level light entry is a leaf whose
+// constants are also those of a record the walker unrolls at the world frame, that record's test
+// has already formed what the entry's hit test would form again (aquad_core's t and accept flag;
+// the sphere's a, half_b and discriminant). The walker then also produces the entries' weights
+// and folds them as gen_lights_pdf does. All or nothing per scene.
+struct LpdfDefer {
+  const rtf::FlatScene* F = nullptr;
+  std::vector<int> world_rec;  // per light entry: the matched world record, -1 = none yet
+
+  static bool same_d(const std::vector<uint32_t>& A, size_t wa, const std::vector<uint32_t>& B,
+                     size_t wb) {  // the same double, bit for bit
+    return A[wa] == B[wb] && A[wa + 1] == B[wb + 1];
+  }
+  // the shape conditions (the matches are found during the walk)
+  bool init(const rtf::FlatScene& Fs) {
+    F = &Fs;
+    const std::vector<uint32_t>& L = Fs.lights;
+    const size_t n = Fs.hdr.n_lights;
+    if (Fs.hdr.has_bvh || Fs.hdr.lights_nested || n == 0 || n > 4 || n > Fs.light_offs.size())
+      return false;
+    int spheres = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t off = Fs.light_offs[i];
+      if (off + 4 > L.size()) return false;
+      const uint32_t ty = L[off] & 0xffu;
+      if (ty == RTL_QUAD) {
+        if (!RTL_QUAD_AXIS(L[off]) || off + RTL_LQUAD_WORDS > L.size()) return false;
+      } else if (ty == RTL_SPHERE) {
+        // one sphere at most: it is sphere_light0, whose cos_theta_max the bounce shares
+        if ((L[off] & RTL_SPHERE_MOVING) || ++spheres > 1 || off + RTL_SPHERE_WORDS > L.size())
+          return false;
+      } else {
+        return false;
+      }
+    }
+    world_rec.assign(n, -1);
+    return true;
+  }
+  // the unmatched light entry with the constants of the world QUAD / SPHERE record at `rec`, or -1
+  int match(const std::vector<uint32_t>& N, size_t rec, uint32_t type) const {
+    const std::vector<uint32_t>& L = F->lights;
+    for (size_t i = 0; i < world_rec.size(); ++i) {
+      const size_t off = F->light_offs[i];
+      if (world_rec[i] >= 0 || (L[off] & 0xffu) != type) continue;
+      bool same = true;
+      if (type == RTL_QUAD) {
+        same = RTL_QUAD_AXIS(N[rec]) == RTL_QUAD_AXIS(L[off]);
+        for (int j = 0; j < 5; ++j)  // q_k and the four accept bounds
+          same = same && same_d(N, rec + 4 + 2 * j, L, off + 4 + 2 * (RTL_LQUAD_AXIS_D + j));
+        const size_t g = rec + RTL_QUAD_GEN;
+        for (int j : {0, 1, 2, 7})  // normal, area (the general payload)
+          same = same && same_d(N, g + 4 + 2 * j, L, off + 4 + 2 * j);
+      } else {
+        same = !(N[rec] & RTL_SPHERE_MOVING);
+        for (int j = 0; j < 4; ++j) same = same && same_d(N, rec + 4 + 2 * j, L, off + 4 + 2 * j);
+      }
+      if (same) return (int)i;
+    }
+    return -1;
+  }
+  bool complete() const {
+    for (int r : world_rec)
+      if (r < 0) return false;
+    return true;
+  }
+};
+
 struct Gen {
   const std::vector<uint32_t>& N;
+  LpdfDefer* lp = nullptr;  // set: the walk also produces the light entries' weights lpv<i>
   std::ostringstream o;
   bool rcp[3] = {false, false, false};  // rcp of d per axis formed in the current frame
   size_t prims = 0;
@@ -162,9 +231,17 @@ struct Gen {
     if (axis) {
       const int k = (int)axis - 1;
       need_rcp(k);
+      const int li = lp && frame < 0 ? lp->match(N, q, RTL_QUAD) : -1;
       o << "    h = aquad_test<COUNT, " << k << ">(AQuad{" << N[q] << "u, " << lit(pd(N, q, 0)) << ", "
         << lit(pd(N, q, 1)) << ", " << lit(pd(N, q, 2)) << ", " << lit(pd(N, q, 3)) << ", "
-        << lit(pd(N, q, 4)) << "}, o, d, mk(rx, ry, rz), tmin, closest, t, C);\n";
+        << lit(pd(N, q, 4)) << "}, o, d, mk(rx, ry, rz), tmin, closest, t, C"
+        << (li >= 0 ? ", lt, lin);\n" : ");\n");
+      if (li >= 0) {  // Quad::pdf_value's test of this ray (gen_light_entry): interval [0.001, inf]
+        lp->world_rec[li] = (int)q;
+        const size_t g = q + RTL_QUAD_GEN;
+        o << "    lpv" << li << " = ((0.001 <= lt) & (lt <= kInf) & lin) ? quad_light_w(d, lt, "
+          << lit3(pd(N, g, 0), pd(N, g, 1), pd(N, g, 2)) << ", " << lit(pd(N, g, 7)) << ") : (wt)0;\n";
+      }
     } else {
       o << "    h = quad_test<COUNT>(N + " << (q + RTL_QUAD_GEN) << "u, o, d, tmin, closest, t, C);\n";
     }
@@ -176,8 +253,15 @@ struct Gen {
     o << "    t = closest;\n    {\n      d3 c = " << lit3(pd(N, s, 0), pd(N, s, 1), pd(N, s, 2)) << ";\n";
     if (N[s] & RTL_SPHERE_MOVING)
       o << "      c = vfma(tm, " << lit3(pd(N, s, 4), pd(N, s, 5), pd(N, s, 6)) << ", c);\n";
-    o << "      h = sphere_test_v<COUNT>(c, " << lit(pd(N, s, 3)) << ", o, d, tmin, closest, t, C);\n"
-      << "    }\n    closest = t;\n    code = h ? " << code(s, frame) << "u : code;\n";
+    const int li = lp && frame < 0 ? lp->match(N, s, RTL_SPHERE) : -1;
+    o << "      h = sphere_test_v<COUNT>(c, " << lit(pd(N, s, 3)) << ", o, d, tmin, closest, t, C"
+      << (li >= 0 ? ", la, lhb, ldisc);\n" : ");\n");
+    if (li >= 0) {  // Sphere::pdf_value's root-free predicate (gen_light_entry, product build)
+      lp->world_rec[li] = (int)s;
+      o << "      const double lc1 = fma(0.001, la, lhb);\n"
+        << "      lpv" << li << " = (!(ldisc < 0.0) & ((lc1 < 0.0) | (ldisc > lc1 * lc1))) ? q_sphere : (wt)0;\n";
+    }
+    o << "    }\n    closest = t;\n    code = h ? " << code(s, frame) << "u : code;\n";
     ++prims;
   }
 };
@@ -371,9 +455,9 @@ bool gen_lights_pdf(const rtf::FlatScene& F, std::ostringstream& o, std::string*
   return true;
 }
 
-}  // namespace
-
-std::string generate(const rtf::FlatScene& F, std::string* why) {
+// The walker of generate(); lp set: with the deferred light-list PDF's by-products (the caller
+// checks lp->complete() afterwards and generates again without when an entry found no record).
+std::string generate_walker(const rtf::FlatScene& F, LpdfDefer* lp, std::string* why) {
   const std::vector<uint32_t>& N = F.nodes;
   if (F.hdr.nested_volumes) {
     *why = "ConstantMedium nested in a volume boundary: the interpreter kernel walks it";
@@ -384,14 +468,23 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
     return "";
   }
   Gen G(N);
+  G.lp = lp;
   std::ostringstream& o = G.o;
   std::ostringstream pre;  // policies the walker refers to (generated volume boundary queries)
   o << "struct TravGen {\n"
        "  template <bool COUNT, bool VOL, bool BVH, bool VOLB, bool VOLI>\n"
        "  static __device__ __forceinline__ bool world(const TraceParams& P, d3& ro, d3& rd, double tm,\n"
-       "      double& t_out, uint32_t& hn, int& hf, Rng& g, Ctr<COUNT>& C) {\n"
+       "      double& t_out, uint32_t& hn, int& hf, Rng& g, Ctr<COUNT>& C"
+    << (lp ? ", wt q_sphere, wt& lsum" : "") << ") {\n"
        "    const kptr N = (kptr)P.nodes;\n"
-       "    (void)N; (void)tm; (void)g;\n"
+       "    (void)N; (void)tm; (void)g;\n";
+  if (lp) {
+    // the light entries' weights for this ray (kLpdfDefer): a matched record's test sets its own
+    o << "    (void)q_sphere;\n    double lt = 0.0, la = 0.0, lhb = 0.0, ldisc = 0.0;\n"
+         "    bool lin = false;\n    (void)lt; (void)la; (void)lhb; (void)ldisc; (void)lin;\n";
+    for (size_t i = 0; i < lp->world_rec.size(); ++i) o << "    wt lpv" << i << " = 0;\n";
+  }
+  o <<
        "    const double tmin = 0.0001;  // render.rs:267\n"
        "    double closest = kInf, t = 0.0;\n"
        "    double rx = 0.0, ry = 0.0, rz = 0.0;\n"
@@ -483,6 +576,12 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
       return "";
     }
   }
+  if (lp) {  // HittableList::pdf_value's fold in the light list's order (gen_lights_pdf)
+    for (size_t i = 0; i < lp->world_rec.size(); ++i)
+      o << (i == 0 ? "    lsum = lpv0;\n" : "    lsum = lsum + lpv" + std::to_string(i) + ";\n");
+    if (F.hdr.lights_is_list)
+      o << "    lsum = lsum * (wt)" << lit(1.0 / (double)lp->world_rec.size()) << ";\n";
+  }
   o << "    t_out = closest;\n"
        "    const bool hit = code != 0u;\n"
        "    uint32_t rn = (code & 0xffffffu) - 1u;\n"
@@ -497,6 +596,13 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
        "    hf = hit ? fr : hf;\n"
        "    return hit;\n"
        "  }\n";
+  if (lp)  // the plain query (no by-products)
+    o << "  template <bool COUNT, bool VOL, bool BVH, bool VOLB, bool VOLI>\n"
+         "  static __device__ __forceinline__ bool world(const TraceParams& P, d3& ro, d3& rd, double tm,\n"
+         "      double& t_out, uint32_t& hn, int& hf, Rng& g, Ctr<COUNT>& C) {\n"
+         "    wt lsum;\n"
+         "    return world<COUNT, VOL, BVH, VOLB, VOLI>(P, ro, rd, tm, t_out, hn, hf, g, C, (wt)0, lsum);\n"
+         "  }\n";
   // The hit record's frame (rt_kernel.h TravInterpN::frame_in / frame_out): every frame the walk
   // can report, its chain unrolled with literals (the same translate/rotate arithmetic as
   // xform_in / xform_out); frames inside BVH subtrees take the interpreter's chain walk.
@@ -559,8 +665,27 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
   std::snprintf(scb, sizeof scb, "  static constexpr uint32_t kScene = 0x%xu;\n", sc);
   // a ray's time is read by moving spheres only (object.rs:107-112): without one the path kernel
   // keeps no time across the bounces
-  o << scb << "  static constexpr bool kMoving = " << (F.has_moving || sc == RTL_SC_ANY ? "true" : "false") << ";\n};\n";
+  o << scb << "  static constexpr bool kMoving = " << (F.has_moving || sc == RTL_SC_ANY ? "true" : "false") << ";\n";
+  // the path kernel leaves a bounce's light-list PDF to the next world query (trace_body DEFER);
+  // -DRT_LPDF_NOW (RT_JIT_OPTS; A/B) evaluates it at the bounce as every other kernel does
+  if (lp)
+    o << "#ifdef RT_LPDF_NOW\n  static constexpr bool kLpdfDefer = false;\n#else\n"
+         "  static constexpr bool kLpdfDefer = true;\n#endif\n};\n";
+  else
+    o << "  static constexpr bool kLpdfDefer = false;\n};\n";
   return pre.str() + o.str();
+}
+
+}  // namespace
+
+std::string generate(const rtf::FlatScene& F, std::string* why) {
+  LpdfDefer lp;
+  if (lp.init(F)) {
+    std::string w = generate_walker(F, &lp, why);
+    if (w.empty() || lp.complete()) return w;
+    why->clear();
+  }
+  return generate_walker(F, nullptr, why);
 }
 
 Flags product_flags(const rtf::FlatScene& F, bool staged) {

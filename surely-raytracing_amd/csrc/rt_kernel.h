@@ -557,7 +557,22 @@ __device__ __forceinline__ void aquad_core(const AQuad& q, d3 o, d3 d, d3 r, dou
 }
 template <bool COUNT, int K>
 __device__ __forceinline__ bool aquad_test(const AQuad& q, d3 o, d3 d, d3 r, double tmin,
+                                           double tmax, double& t_out, Ctr<COUNT>& C,
+                                           double& t_plane, bool& plane_inr);
+template <bool COUNT, int K>
+__device__ __forceinline__ bool aquad_test(const AQuad& q, d3 o, d3 d, d3 r, double tmin,
                                            double tmax, double& t_out, Ctr<COUNT>& C) {
+  double t_plane;
+  bool plane_inr;
+  return aquad_test<COUNT, K>(q, o, d, r, tmin, tmax, t_out, C, t_plane, plane_inr);
+}
+// The same test, also handing out what it formed before the interval: the plane quotient t and
+// plane & inr. A generated walker (rt_jit.cpp, kLpdfDefer) answers the light-list PDF's hit test
+// of the same ray against the same quad from them, with that test's own interval.
+template <bool COUNT, int K>
+__device__ __forceinline__ bool aquad_test(const AQuad& q, d3 o, d3 d, d3 r, double tmin,
+                                           double tmax, double& t_out, Ctr<COUNT>& C,
+                                           double& t_plane, bool& plane_inr) {
   C.inc(RT_OP_QUAD_TESTS);
   const double dk = comp<K>(d);
   double t;
@@ -570,6 +585,8 @@ __device__ __forceinline__ bool aquad_test(const AQuad& q, d3 o, d3 d, d3 r, dou
   C.inc_if(RT_OP_QUAD_PLANE, plane);
   C.inc_if(RT_OP_QUAD_INTERVAL, range);
   C.inc_if(RT_OP_QUAD_HITS, hit);
+  t_plane = t;
+  plane_inr = plane & inr;
   t_out = hit ? t : t_out;
   return hit;
 }
@@ -614,15 +631,29 @@ __device__ __forceinline__ bool sphere_test(Ptr s, d3 o, d3 d, double tm, double
 }
 // sphere_test on a center (at the ray's time) and radius already in registers; the generated
 // scene walkers (rt_jit.cpp) pass them as literals.
+// The overload with trailing out-parameters also hands out a, half_b and the discriminant (a
+// generated walker's deferred light-list PDF, rt_jit.cpp kLpdfDefer, forms the root-free
+// predicate of light_leaf_pdf from them).
+template <bool COUNT>
+__device__ __forceinline__ bool sphere_test_v(d3 center, double r, d3 o, d3 d, double tmin,
+                                              double tmax, double& t_out, Ctr<COUNT>& C,
+                                              double& a, double& half_b, double& disc);
 template <bool COUNT>
 __device__ __forceinline__ bool sphere_test_v(d3 center, double r, d3 o, d3 d, double tmin,
                                               double tmax, double& t_out, Ctr<COUNT>& C) {
+  double a, half_b, disc;
+  return sphere_test_v<COUNT>(center, r, o, d, tmin, tmax, t_out, C, a, half_b, disc);
+}
+template <bool COUNT>
+__device__ __forceinline__ bool sphere_test_v(d3 center, double r, d3 o, d3 d, double tmin,
+                                              double tmax, double& t_out, Ctr<COUNT>& C,
+                                              double& a, double& half_b, double& disc) {
   C.inc(RT_OP_SPHERE_TESTS);
   d3 oc = o - center;
-  double a = dot(d, d);
-  double half_b = dot(oc, d);
+  a = dot(d, d);
+  half_b = dot(oc, d);
   double c = dot(oc, oc) - r * r;
-  double disc = fma(half_b, half_b, -(a * c));
+  disc = fma(half_b, half_b, -(a * c));
   // straight-line: both roots are formed and the predicate selects (object.rs:157-166); a
   // negative discriminant gives NaN roots, which the predicate never reads
   const bool real = !(disc < 0.0);
@@ -2035,6 +2066,8 @@ template <int VN>
 struct TravInterpN {
   static constexpr uint32_t kScene = kScAny;
   static constexpr bool kMoving = true;  // the scene may hold moving spheres (a ray's time is read)
+  // no deferred light-list PDF: world() hands out no light-list hit results (rt_jit.cpp)
+  static constexpr bool kLpdfDefer = false;
   template <bool COUNT, bool VOL, bool BVH, bool VOLB, bool VOLI>
   static __device__ __forceinline__ bool world(const TraceParams& P, d3& ro, d3& rd, double tm,
                                                double& t, uint32_t& hn, int& hf, Rng& g,
@@ -2179,8 +2212,20 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   // take the exec-masked writes of the branches as they are. (The BVH kernels' LDS holds the
   // compact trees; they keep registers, and do not spill there.)
   constexpr bool LDSF = !BVH;
-  __shared__ wt sh_f[LDSF ? 3 * NB : 1];
-  __shared__ wt sh_le[LDSF ? 3 * NB : 1];
+  // Deferred light-list PDF (product build, generated walkers whose every light entry is also a
+  // world-frame record, rt_jit.cpp kLpdfDefer): a Lambertian / Isotropic bounce scatters along
+  // (p, dir), and the next iteration's world query tests that very ray against the same quad /
+  // sphere constants, so the bounce leaves the mixture's light-list value to that query. The lane
+  // parks the operands of its factor in its LDS slots (atten in the factor's, then s_pdf, mat_pdf
+  // and the sphere light's weight), sets kLpPend in the depth word and commits no factor; right
+  // after the query the same arithmetic on the same operands finishes beta. A lane on its last
+  // bounce has no next query (and the reference still needs pdf_val == 0 there): it takes the
+  // immediate path. An ending lane writes its radiance only after it has consumed its factor, so
+  // the radiance shares the factor's slots: the six slots per lane cost no LDS over sh_f + sh_le.
+  constexpr bool DEFER = !COUNT && LDSF && Trav::kLpdfDefer;
+  constexpr int kLpPend = (int)(16u << 24);  // above RT_XS_*
+  constexpr int LE0 = DEFER ? 0 : 3 * NB;    // the ending radiance's first slot
+  __shared__ wt sh_f[LDSF ? 6 * NB : 1];
   // Non-BVH kernels: the first round of the item's stream key (rt_rng.h), its pixel term and the
   // sample term of the item's next sample, formed at the claim; a camera ray then costs one add
   // and the hash's two remaining rounds instead of the pixel and sample indices and the round
@@ -2407,7 +2452,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     w3 f_next;          // this bounce's throughput factor
     auto set_le = [&](w3 v) {
       if constexpr (LDSF) {
-        sh_le[tid] = v.x, sh_le[NB + tid] = v.y, sh_le[2 * NB + tid] = v.z;
+        sh_f[LE0 + tid] = v.x, sh_f[LE0 + NB + tid] = v.y, sh_f[LE0 + 2 * NB + tid] = v.z;
       } else {
         Le = v;
       }
@@ -2448,7 +2493,32 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       asm volatile("" ::"v"(t2), "v"(hn2), "v"(hf2), "v"(g2.s0));
     }
 #endif
-    if (!Trav::template world<COUNT, VOL, BVH, VOLB, VOLI>(P, ro, rd, tm, t, hn, hf, g, C)) {
+    bool hit_w;
+    if constexpr (DEFER) {
+      // the query also folds the light list's value for its ray (the previous bounce's scattered
+      // ray); pending lanes finish that bounce's factor before anything reads beta
+      wt lsum;
+      hit_w = Trav::template world<COUNT, VOL, BVH, VOLB, VOLI>(P, ro, rd, tm, t, hn, hf, g, C,
+                                                                sh_f[5 * NB + tid], lsum);
+      if (depth & kLpPend) {
+        const w3 atten = mkw(sh_f[tid], sh_f[NB + tid], sh_f[2 * NB + tid]);
+        const wt s_pdf = sh_f[3 * NB + tid], mat_pdf = sh_f[4 * NB + tid];
+        const wt pdf_val = fma((wt)0.5, lsum, (wt)0.5 * mat_pdf);  // pdf.rs:116
+        w3 factor = atten * (s_pdf * rcp_wt(pdf_val));
+        depth &= ~kLpPend;
+#ifndef RT_ABL_NOXS
+        if (!(pdf_val != (wt)0)) {  // as the immediate path below
+          depth |= (int)((RT_XS_ON | xs_nan_bits(atten * s_pdf, beta)) << 24);
+          beta = mkw(1, 1, 1);
+          factor = beta;
+        }
+#endif
+        beta = beta * factor;
+      }
+    } else {
+      hit_w = Trav::template world<COUNT, VOL, BVH, VOLB, VOLI>(P, ro, rd, tm, t, hn, hf, g, C);
+    }
+    if (!hit_w) {
       C.inc(RT_OP_MISSES);  // background render.rs:298-309
       set_le(beta * to_w3(karr3(kparams()->bg)));
       term = emit_end = true;
@@ -2664,27 +2734,40 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       }
       wt pdf_val = mat_pdf;
       PROF(5);
+      bool lp_now = true;  // the light-list PDF is evaluated at this bounce
+      if constexpr (DEFER) {
+        if (have_lights && (depth & 0xffffff) != 1) {  // not the last bounce: the next query
+          lp_now = false;
+          sh_f[3 * NB + tid] = s_pdf, sh_f[4 * NB + tid] = mat_pdf;
+          if constexpr ((SC & kScLSphere) != 0u) sh_f[5 * NB + tid] = sphere_light_w(cos_sl);
+          depth |= kLpPend;
+          factor = atten;  // parked in the factor's slots; the commit skips pending lanes
+        }
+      }
+      if (DEFER ? (__ballot(lp_now) != 0ull && lp_now) : true) {
 #ifndef RT_ABL_NOLPDF  // ablation build: no light-PDF evaluation (weights only; same paths)
-      if (have_lights)  // pdf.rs:116
-        pdf_val = fma((wt)0.5, Trav::template lights_pdf<COUNT>(P, p, dir, cos_sl, C), (wt)0.5 * mat_pdf);
+        if (have_lights)  // pdf.rs:116
+          pdf_val = fma((wt)0.5, Trav::template lights_pdf<COUNT>(P, p, dir, cos_sl, C),
+                        (wt)0.5 * mat_pdf);
 #ifdef RT_ABL_LPDF2  // ablation build: the light PDF evaluated twice (same result)
-      if (have_lights) {
-        d3 p2 = p;
-        asm volatile("" : "+v"(p2.x));
-        const wt lp2 = Trav::template lights_pdf<COUNT>(P, p2, dir, cos_sl, C);
-        asm volatile("" ::"v"(lp2));
-      }
+        if (have_lights) {
+          d3 p2 = p;
+          asm volatile("" : "+v"(p2.x));
+          const wt lp2 = Trav::template lights_pdf<COUNT>(P, p2, dir, cos_sl, C);
+          asm volatile("" ::"v"(lp2));
+        }
 #endif
 #endif
-      PROF(6);
-      factor = atten * (s_pdf * rcp_wt(pdf_val));
+        PROF(6);
+        factor = atten * (s_pdf * rcp_wt(pdf_val));
 #ifndef RT_ABL_NOXS  // ablation build: no special-value tracking (cost of RT_XS_*)
-      if (!(pdf_val != (wt)0)) {  // pdf_val 0 or NaN: the sample becomes inf / NaN (RT_XS_ON)
-        depth |= (int)((RT_XS_ON | xs_nan_bits(atten * s_pdf, beta)) << 24);
-        beta = mkw(1, 1, 1);
-        factor = beta;
-      }
+        if (!(pdf_val != (wt)0)) {  // pdf_val 0 or NaN: the sample becomes inf / NaN (RT_XS_ON)
+          depth |= (int)((RT_XS_ON | xs_nan_bits(atten * s_pdf, beta)) << 24);
+          beta = mkw(1, 1, 1);
+          factor = beta;
+        }
 #endif
+      }
     } else {
       // reflect (vec3.rs:219-221) or refract (vec3.rs:223-229; its cos_theta is cos_t)
       const d3 perp = ratio * vfma(cos_t, normal, uu);
@@ -2700,6 +2783,10 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       ro = p_next;
       rd = d_next;
       if constexpr (LDSF) f_next = mkw(sh_f[tid], sh_f[NB + tid], sh_f[2 * NB + tid]);
+      if constexpr (DEFER) {  // a pending lane's slots hold atten: its factor comes after the query
+        const bool pend = (depth & kLpPend) != 0;
+        f_next = mkw(pend ? (wt)1 : f_next.x, pend ? (wt)1 : f_next.y, pend ? (wt)1 : f_next.z);
+      }
       beta = beta * f_next;
       // the product is formed here: left to itself the compiler sinks it to beta's next use (the
       // following bounce, past the pool scheduling and the camera-ray block), which keeps the
@@ -2713,7 +2800,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     if (term & alive) {
       if constexpr (LDSF) {
-        if (emit_end) Le = mkw(sh_le[tid], sh_le[NB + tid], sh_le[2 * NB + tid]);
+        if (emit_end) Le = mkw(sh_f[LE0 + tid], sh_f[LE0 + NB + tid], sh_f[LE0 + 2 * NB + tid]);
       }
       end_sample(emit_end ? to_d3(Le) : mk(0., 0., 0.));
     }
