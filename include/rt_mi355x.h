@@ -315,6 +315,49 @@ void rt_multi_destroy(rt_multi* multi);
 int rt_render_blob(const rt_scene_blob* blob, const rt_camera* cam, const rt_render_opts* opts,
                    float* accum_rgb, rt_stats* stats);
 
+/* ---- first-hit AOV pass --------------------------------------------------------------------
+ * The guides a denoiser or compositor wants next to the beauty sums, and a flip-free view of
+ * primary visibility: every pixel-sample of the call (same rows, strata, seed and therefore the
+ * same RNG stream as rt_render_device) forms its camera ray as the beauty pass does (jitter,
+ * defocus disk, time), runs ONE world query over [1e-4, inf) with the sample's own generator and
+ * writes what it found. cam->max_depth is ignored. Output: n_rows * W * RT_AOV_CHANNELS floats,
+ * pixel-interleaved. Channels 0-10 are sums over the call's samples (f64 per pixel in the
+ * reference's sample order, rounded once to f32):
+ *   RT_AOV_HITS      1 per hit (coverage = hits / spp)
+ *   RT_AOV_T         rec.t: the RAY PARAMETER of the reference's unnormalised camera ray
+ *                    (direction = pixel sample - origin), not a Euclidean distance; 0 on a miss
+ *   RT_AOV_NORMAL    rec.normal after set_face_normal, world space (3); a ConstantMedium hit has
+ *                    (1,0,0) (constant_medium.rs:82-90); 0 on a miss
+ *   RT_AOV_ALBEDO    the attenuation the first bounce would multiply by (3): tex.value(u,v,p) for
+ *                    Lambertian and Isotropic, Metal's albedo, Dielectric's tint, 0 for
+ *                    DiffuseLight; 0 on a miss
+ *   RT_AOV_EMISSION  ray_color at depth 1 (3): DiffuseLight's tex.value(u,v,p) when front_face,
+ *                    0 for every other hit, cam->background on a miss
+ *   RT_AOV_MATID     NOT a sum: the blob material-table index hit by the call's first sample
+ *                    (first stratum row of the call, s_i = 0), -1 on a miss; always overwritten
+ * Without RT_FLAG_OVERWRITE channels 0-10 are added into the buffer, (float)((double)a + sum).
+ * RT_FLAG_REFERENCE_BVH is honoured; RT_FLAG_INTERPRETER and RT_FLAG_SEMANTICS_REFERENCE are
+ * accepted (neither changes a first hit); RT_FLAG_COUNT_OPS is RT_ERR_INVALID_ARG. Limits, status
+ * codes, the split of tall row ranges, re-entrancy and lifetime are those of rt_render_device; a
+ * call with n_rows == 0 returns RT_OK and touches nothing. rt_stats: ms_kernel, ms_total, samples;
+ * launches = AOV kernel launches; out_bytes = bytes written; ops all zero. */
+#define RT_AOV_CHANNELS 12
+#define RT_AOV_HITS 0
+#define RT_AOV_T 1
+#define RT_AOV_NORMAL 2
+#define RT_AOV_ALBEDO 5
+#define RT_AOV_EMISSION 8
+#define RT_AOV_MATID 11
+
+/* Synchronous: AOVs into a HOST buffer (n_rows * W * RT_AOV_CHANNELS floats). */
+int rt_render_aov(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                  float* aov_host, rt_stats* stats);
+
+/* Asynchronous on `hip_stream` (may be NULL): AOVs into a DEVICE buffer. If stats != NULL the
+ * call synchronises the stream to fill it. */
+int rt_render_aov_device(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                         float* aov_device, void* hip_stream, rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

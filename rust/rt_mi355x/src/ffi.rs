@@ -53,6 +53,15 @@ pub const RT_LAYOUT_STATS: c_int = 11;
 pub const RT_LDS_CHECK: c_int = 19;
 pub const RT_TRACE_HISTORY: c_int = 64;
 
+// first-hit AOV pass: floats per pixel and the channel offsets
+pub const RT_AOV_CHANNELS: usize = 12;
+pub const RT_AOV_HITS: usize = 0;
+pub const RT_AOV_T: usize = 1;
+pub const RT_AOV_NORMAL: usize = 2;
+pub const RT_AOV_ALBEDO: usize = 5;
+pub const RT_AOV_EMISSION: usize = 8;
+pub const RT_AOV_MATID: usize = 11;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -164,4 +173,10 @@ extern "C" {
     pub fn rt_render_blob(blob: *const rt_scene_blob, cam: *const rt_camera,
                           opts: *const rt_render_opts, accum_rgb: *mut f32,
                           stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_aov(scene: *mut rt_scene, cam: *const rt_camera,
+                         opts: *const rt_render_opts, aov_host: *mut f32,
+                         stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_aov_device(scene: *mut rt_scene, cam: *const rt_camera,
+                                opts: *const rt_render_opts, aov_device: *mut f32,
+                                hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
 }

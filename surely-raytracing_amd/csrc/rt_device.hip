@@ -38,8 +38,10 @@
 #include "rt_jit.hpp"
 #include "rt_kernel.h"
 #include "rt_layout.h"
+#include "rt_scene_impl.hpp"
 
 using namespace rtk;
+using namespace rts;
 
 namespace {
 
@@ -196,36 +198,16 @@ __global__ __launch_bounds__(256) void rt_deinterleave(float* __restrict__ stage
 // ---------------------------------------------------------------- host side
 thread_local std::string g_err;
 
-int set_err(int code, const std::string& m) {
+}  // namespace
+
+int rts::set_err(int code, const std::string& m) {
   g_err = m;
   return code;
 }
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-  } while (0)
-
-// The path kernel's LDS for one render (rt_trace's prologue stages these regions, in this order,
-// from byte 0 of the dynamic LDS): the small tables or the Perlin tables (stage), then either the
-// compact ordered BVHs and the LDS walk's per-lane stacks (cbvh_walk_t: lane l's slot k at
-// stack_off + 4 (l + k block), header cbvh_stack = 4 x the deepest tree's depth bytes per lane),
-// or as much of the reference BVH region as fits. One function for the render and for the host
-// check of the plan (rt_scene_lds_check), so the two cannot drift apart.
-struct LdsPlan {
-  int block = 0;
-  size_t static_lds = 0;  // the kernel's static LDS (per-lane f64 sums, ...), an upper bound
-  uint32_t stage_scene = 0, stage_bytes = 0, n_perlin_lds = 0;
-  uint32_t cbvh_lds_off = ~0u, stack_lds_off = 0, cbvh_bytes = 0;
-  size_t cbvh_lds = 0;  // bytes of the trees and stacks
-  uint32_t bvh_lds_words = 0, bvh_lds_off = 0;
-  uint32_t row_lds_off = ~0u;  // BVH kernels: the row items' row totals (~0u: no row items)
-  size_t lds_bytes = 0;  // dynamic LDS of the launch
-};
-LdsPlan plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32_t flags, bool want_jit,
-                 size_t lds_module_max) {
+// The launch's LDS plan (LdsPlan, rt_scene_impl.hpp)
+LdsPlan rts::plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32_t flags, bool want_jit,
+                      size_t lds_module_max) {
   LdsPlan L;
   const bool count = (flags & RT_FLAG_COUNT_OPS) != 0;
   const bool bvh = hdr.has_bvh != 0;
@@ -279,6 +261,8 @@ LdsPlan plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32_t flags, b
   return L;
 }
 
+namespace {
+
 // Byte offsets of the scene's tables in its one device allocation (rt_scene_create): nodes,
 // materials, textures, lights, light offsets, Perlin tables, 16-byte aligned; texels last.
 struct TableLayout {
@@ -300,56 +284,6 @@ TableLayout table_layout(const rtf::FlatScene& F) {
 }
 
 }  // namespace
-
-// The per-render state of a scene: the f64 workspace, the pool-queue word and op counters, the
-// stats events and a completion event. A render takes a slot that no render still uses (its done
-// event has fired) or one whose last render went to the same stream (stream order then protects
-// it); otherwise a new slot is made (up to kMaxSlots), so renders of one scene on different
-// streams or host threads run concurrently on their own queue words and workspaces.
-struct RenderSlot {
-  uint8_t* work = nullptr;  // row totals / segment partials / tail samples + f64 running sums
-  size_t work_bytes = 0;
-  unsigned long long* ops = nullptr;  // 32 op counters, the pool-queue word (32), profiling (40..)
-  unsigned int* queue = nullptr;
-  hipEvent_t done = nullptr;  // recorded after the render's last kernel
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // rt_stats::ms_kernel
-  hipStream_t last_stream = nullptr;
-  bool recorded = false;  // `done` has been recorded at least once
-  bool held = false;      // a render call is between acquire and release
-};
-
-struct rt_scene {
-  int device = 0;
-  rtl_scene_header hdr{};
-  uint8_t* dev = nullptr;  // one allocation for all tables
-  uint64_t dev_bytes = 0;
-  const uint32_t *nodes = nullptr, *mats = nullptr, *texs = nullptr, *lights = nullptr,
-                 *light_offs = nullptr;
-  const uint8_t *perlin = nullptr, *texels = nullptr;
-  uint32_t o_mats = 0, o_texs = 0, o_lights = 0, o_loffs = 0, o_perl = 0;  // byte offsets in dev
-  int sphere_light0 = -1;  // first SPHERE light record (TraceParams::sphere_light0)
-  static constexpr int kMaxSlots = 8;
-  std::vector<std::unique_ptr<RenderSlot>> slots;  // grown on demand (RenderSlot)
-  int last_slot = -1;                              // the slot of the latest render
-  std::condition_variable slot_cv;                 // a held slot was released
-  int n_cu = 0;                 // compute units of the device
-  size_t mem_total = (size_t)8 << 30;  // device memory (hipMemGetInfo at creation)
-  size_t lds_module_max = 64u << 10;  // LDS a module (hiprtc) launch may take (device limit)
-  int resident_blocks[48] = {}; // per kernel variant: blocks resident per CU (0 = not queried)
-  size_t resident_lds[48] = {};  // ... at this dynamic LDS size
-  // scene-specialised product kernel (rt_jit.cpp): the generated world walker, compiled on the
-  // first product render. jit_state: 0 = not compiled yet, 1 = compiled, -1 = scene not
-  // generated (jit_msg says why), -2 = compile failed (jit_msg = log; the interpreter runs)
-  std::string jit_walker, jit_msg;
-  int jit_state = -1;
-  rtj::Kernel jit_k[4];  // [tex][staged]
-  // rt_trace launch timing: one event pair per launch, ring of kTraceRing, tagged by render id
-  static constexpr int kTraceRing = 4 * RT_TRACE_HISTORY;
-  hipEvent_t tev[kTraceRing][2] = {};
-  uint64_t tev_render[kTraceRing] = {};
-  uint64_t n_tev = 0, n_render = 0;
-  std::mutex mu;
-};
 
 extern "C" {
 
@@ -584,13 +518,11 @@ int rt_scene_jit_info(rt_scene* sc, int* state, char* msg, uint32_t msg_len) {
   return RT_OK;
 }
 
-// A slot for a render on `stream` (RenderSlot), with sc->mu held through `lock`: a free one (its
-// last render has finished, or went to the same stream handle), else a new one, else wait for a
-// release. A reused slot's `done` event is always waited for on `stream` (hipStreamWaitEvent):
-// equal handles are not the same stream everywhere (hipStreamPerThread, the per-thread default
-// stream), so stream order alone cannot be trusted; on the same stream the wait costs nothing.
-static int acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStream_t stream,
-                        RenderSlot** out) {
+}  // extern "C"
+
+// A slot for a render on `stream` (rt_scene_impl.hpp)
+int rts::acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStream_t stream,
+                      RenderSlot** out) {
   for (;;) {
     RenderSlot* pick = nullptr;
     for (const auto& sl : sc->slots) {
@@ -645,33 +577,6 @@ static int acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStr
     return RT_OK;
   }
 }
-
-// Releases a held slot on every exit path of a render call. Once the call has enqueued work on
-// `stream` (enqueued), a call that fails half way still records the slot's `done` event after
-// that work: the next render to take the slot then waits for the kernels that may still use its
-// workspace and queue word, instead of for the previous render's event.
-struct SlotHold {
-  rt_scene* sc;
-  std::unique_lock<std::mutex>& lock;
-  RenderSlot* sl = nullptr;
-  hipStream_t stream = nullptr;
-  bool enqueued = false;   // work of this call is on `stream`
-  bool finished = false;   // `done` was recorded after all of it
-  ~SlotHold() {
-    if (!sl) return;
-    if (!lock.owns_lock()) lock.lock();
-    if (enqueued && !finished) {
-      if (hipEventRecord(sl->done, stream) == hipSuccess) {
-        sl->recorded = true;
-        sl->last_stream = stream;
-      } else {
-        (void)hipStreamSynchronize(stream);  // no event: drain the stream before the slot is reused
-      }
-    }
-    sl->held = false;
-    sc->slot_cv.notify_all();
-  }
-};
 
 static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
                               float* accum, void* stream_v, rt_stats* stats) {
@@ -1033,10 +938,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   return RT_OK;
 }
 
-// Lane item keys hold the call's row index in 15 bits (render_device_rows): taller row ranges
-// are rendered as consecutive sub-calls of kRowsPerCall rows into the matching rows of accum.
-// The RNG is keyed by the global pixel and sample, so the image does not depend on the split.
-constexpr int kRowsPerCall = 32760;
+extern "C" {
 
 int rt_render_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
                      float* accum, void* stream_v, rt_stats* stats) {

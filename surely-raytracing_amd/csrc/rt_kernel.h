@@ -2524,7 +2524,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       term = emit_end = true;
       break;
     }
-    // ---- hit record of the winning primitive, recomputed in its own frame (deferred)
+    // ---- hit record of the winning primitive, recomputed in its own frame (deferred).
+    // The first-hit AOV pass keeps a second copy of this block (rt_aov.h aov_body);
+    // tests/test_aov_gpu.py pins the two together. Change one, change the other.
     PROF(2);
     const TP X = T.nodes + hn;
     uint32_t type = X[0] & 0xffu;

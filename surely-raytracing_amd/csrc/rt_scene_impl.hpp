@@ -1,0 +1,148 @@
+// rt_scene_impl.hpp — the host-side scene and render-slot types shared by the translation units of
+// librtmi355x.so that launch kernels on a scene: rt_device.hip (the path kernels and the C ABI's
+// scene functions, where everything declared here is defined) and rt_aov.hip (the first-hit AOV
+// pass). Internal: nothing here is part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <condition_variable>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "rt_mi355x.h"
+#include "rt_jit.hpp"
+#include "rt_layout.h"
+
+#define RTS_HIDDEN __attribute__((visibility("hidden")))
+
+namespace rts {
+
+// status code + the thread's rt_last_error() message
+RTS_HIDDEN int set_err(int code, const std::string& m);
+
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess)                                                                    \
+      return rts::set_err(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
+  } while (0)
+
+// The path kernel's LDS for one render (rt_trace's prologue stages these regions, in this order,
+// from byte 0 of the dynamic LDS): the small tables or the Perlin tables (stage), then either the
+// compact ordered BVHs and the LDS walk's per-lane stacks (cbvh_walk_t: lane l's slot k at
+// stack_off + 4 (l + k block), header cbvh_stack = 4 x the deepest tree's depth bytes per lane),
+// or as much of the reference BVH region as fits. One function for the render, for the AOV pass
+// (whose kernel runs the same walker on the same plan) and for the host check of the plan
+// (rt_scene_lds_check), so they cannot drift apart.
+struct LdsPlan {
+  int block = 0;
+  size_t static_lds = 0;  // the kernel's static LDS (per-lane f64 sums, ...), an upper bound
+  uint32_t stage_scene = 0, stage_bytes = 0, n_perlin_lds = 0;
+  uint32_t cbvh_lds_off = ~0u, stack_lds_off = 0, cbvh_bytes = 0;
+  size_t cbvh_lds = 0;  // bytes of the trees and stacks
+  uint32_t bvh_lds_words = 0, bvh_lds_off = 0;
+  uint32_t row_lds_off = ~0u;  // BVH kernels: the row items' row totals (~0u: no row items)
+  size_t lds_bytes = 0;  // dynamic LDS of the launch
+};
+RTS_HIDDEN LdsPlan plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32_t flags,
+                            bool want_jit, size_t lds_module_max);
+
+}  // namespace rts
+
+// The per-render state of a scene: the f64 workspace, the pool-queue word and op counters, the
+// stats events and a completion event. A render takes a slot that no render still uses (its done
+// event has fired) or one whose last render went to the same stream (stream order then protects
+// it); otherwise a new slot is made (up to kMaxSlots), so renders of one scene on different
+// streams or host threads run concurrently on their own queue words and workspaces.
+struct RenderSlot {
+  uint8_t* work = nullptr;  // row totals / segment partials / tail samples + f64 running sums
+  size_t work_bytes = 0;
+  unsigned long long* ops = nullptr;  // 32 op counters, the pool-queue word (32), profiling (40..)
+  unsigned int* queue = nullptr;
+  hipEvent_t done = nullptr;  // recorded after the render's last kernel
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // rt_stats::ms_kernel
+  hipStream_t last_stream = nullptr;
+  bool recorded = false;  // `done` has been recorded at least once
+  bool held = false;      // a render call is between acquire and release
+};
+
+struct rt_scene {
+  int device = 0;
+  rtl_scene_header hdr{};
+  uint8_t* dev = nullptr;  // one allocation for all tables
+  uint64_t dev_bytes = 0;
+  const uint32_t *nodes = nullptr, *mats = nullptr, *texs = nullptr, *lights = nullptr,
+                 *light_offs = nullptr;
+  const uint8_t *perlin = nullptr, *texels = nullptr;
+  uint32_t o_mats = 0, o_texs = 0, o_lights = 0, o_loffs = 0, o_perl = 0;  // byte offsets in dev
+  int sphere_light0 = -1;  // first SPHERE light record (TraceParams::sphere_light0)
+  static constexpr int kMaxSlots = 8;
+  std::vector<std::unique_ptr<RenderSlot>> slots;  // grown on demand (RenderSlot)
+  int last_slot = -1;                              // the slot of the latest render
+  std::condition_variable slot_cv;                 // a held slot was released
+  int n_cu = 0;                 // compute units of the device
+  size_t mem_total = (size_t)8 << 30;  // device memory (hipMemGetInfo at creation)
+  size_t lds_module_max = 64u << 10;  // LDS a module (hiprtc) launch may take (device limit)
+  int resident_blocks[48] = {}; // per kernel variant: blocks resident per CU (0 = not queried)
+  size_t resident_lds[48] = {};  // ... at this dynamic LDS size
+  int aov_resident[8] = {};      // the same per rt_aov variant (rt_aov.hip)
+  size_t aov_resident_lds[8] = {};
+  // scene-specialised product kernel (rt_jit.cpp): the generated world walker, compiled on the
+  // first product render. jit_state: 0 = not compiled yet, 1 = compiled, -1 = scene not
+  // generated (jit_msg says why), -2 = compile failed (jit_msg = log; the interpreter runs)
+  std::string jit_walker, jit_msg;
+  int jit_state = -1;
+  rtj::Kernel jit_k[4];  // [tex][staged]
+  // rt_trace launch timing: one event pair per launch, ring of kTraceRing, tagged by render id
+  static constexpr int kTraceRing = 4 * RT_TRACE_HISTORY;
+  hipEvent_t tev[kTraceRing][2] = {};
+  uint64_t tev_render[kTraceRing] = {};
+  uint64_t n_tev = 0, n_render = 0;
+  std::mutex mu;
+};
+
+namespace rts {
+
+// A slot for a render on `stream` (RenderSlot), with sc->mu held through `lock`: a free one (its
+// last render has finished, or went to the same stream handle), else a new one, else wait for a
+// release. A reused slot's `done` event is always waited for on `stream` (hipStreamWaitEvent):
+// equal handles are not the same stream everywhere (hipStreamPerThread, the per-thread default
+// stream), so stream order alone cannot be trusted; on the same stream the wait costs nothing.
+RTS_HIDDEN int acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStream_t stream,
+                            RenderSlot** out);
+
+// Releases a held slot on every exit path of a render call. Once the call has enqueued work on
+// `stream` (enqueued), a call that fails half way still records the slot's `done` event after
+// that work: the next render to take the slot then waits for the kernels that may still use its
+// workspace and queue word, instead of for the previous render's event.
+struct SlotHold {
+  rt_scene* sc;
+  std::unique_lock<std::mutex>& lock;
+  RenderSlot* sl = nullptr;
+  hipStream_t stream = nullptr;
+  bool enqueued = false;   // work of this call is on `stream`
+  bool finished = false;   // `done` was recorded after all of it
+  ~SlotHold() {
+    if (!sl) return;
+    if (!lock.owns_lock()) lock.lock();
+    if (enqueued && !finished) {
+      if (hipEventRecord(sl->done, stream) == hipSuccess) {
+        sl->recorded = true;
+        sl->last_stream = stream;
+      } else {
+        (void)hipStreamSynchronize(stream);  // no event: drain the stream before the slot is reused
+      }
+    }
+    sl->held = false;
+    sc->slot_cv.notify_all();
+  }
+};
+
+// Lane item keys hold the call's row index in 15 bits (render_device_rows): taller row ranges
+// are rendered as consecutive sub-calls of kRowsPerCall rows into the matching rows of accum.
+// The RNG is keyed by the global pixel and sample, so the image does not depend on the split.
+constexpr int kRowsPerCall = 32760;
+
+}  // namespace rts

@@ -37,6 +37,12 @@ RT_FLAG_SEMANTICS_REFERENCE = 0x4
 RT_FLAG_INTERPRETER = 0x8  # product render with the interpreter walker (no scene-specialised kernel)
 RT_FLAG_REFERENCE_BVH = 0x10  # product render walks BVH subtrees in the reference tree and order
 
+# first-hit AOV pass (include/rt_mi355x.h RT_AOV_*): channels per pixel and their offsets
+AOV_CHANNELS = 12
+AOV_HITS, AOV_T, AOV_NORMAL, AOV_ALBEDO, AOV_EMISSION, AOV_MATID = 0, 1, 2, 5, 8, 11
+AOV_NAMES = ("hits", "t", "nx", "ny", "nz", "albedo_r", "albedo_g", "albedo_b",
+             "emission_r", "emission_g", "emission_b", "matid")
+
 OP_NAMES = [
     "samples", "world_queries", "quad_tests", "quad_plane", "quad_interval", "quad_hits",
     "sphere_tests", "sphere_roots", "sphere_hits", "aabb_tests", "translate", "rotate_y",
@@ -183,6 +189,10 @@ def load_device_lib(path: Path) -> C.CDLL:
                                 C.POINTER(RtStats)]),
         "rt_render_device": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
                                        C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_aov": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_void_p,
+                                    C.POINTER(RtStats)]),
+        "rt_render_aov_device": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
+                                           C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -469,6 +479,30 @@ class DeviceScene:
                                               C.byref(st) if st is not None else None))
         return st
 
+    def render_aov(self, cam: RtCamera, opts: RtRenderOpts, aov: np.ndarray | None = None):
+        """Synchronous first-hit AOV pass (rt_render_aov) into a host float32
+        (n_rows, W, AOV_CHANNELS) array: per-pixel sums over the call's samples of hits, t (the
+        ray parameter of the unnormalised camera ray), normal, albedo and emission, and the first
+        sample's material id (aov_planes names them); returns (aov, stats). Without
+        RT_FLAG_OVERWRITE the sums are added into `aov`."""
+        shape = (opts.n_rows, cam.image_width, AOV_CHANNELS)
+        if aov is None:
+            aov = np.zeros(shape, np.float32)
+        assert aov.shape == shape and aov.dtype == np.float32 and aov.flags.c_contiguous
+        st = RtStats()
+        _check_dev(self._lib.rt_render_aov(self._h, C.byref(cam), C.byref(opts), aov.ctypes.data,
+                                           C.byref(st)))
+        return aov, st
+
+    def render_aov_device(self, cam: RtCamera, opts: RtRenderOpts, dev_ptr: int, stream: int = 0,
+                          stats: bool = False):
+        """Asynchronous AOV pass into a device buffer of n_rows * W * AOV_CHANNELS floats."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_render_aov_device(self._h, C.byref(cam), C.byref(opts),
+                                                  C.c_void_p(dev_ptr), C.c_void_p(stream or None),
+                                                  C.byref(st) if st is not None else None))
+        return st
+
     def jit_info(self) -> tuple[int, str]:
         """(state, message) of the scene-specialised kernel: 1 compiled and in use, 0 not compiled
         yet, -1 not generated for this scene, -2 compilation failed (rt_scene_jit_info)."""
@@ -483,6 +517,17 @@ class DeviceScene:
         got = C.c_int(0)
         _check_dev(self._lib.rt_scene_trace_ms(self._h, buf, n, C.byref(got)))
         return [float(buf[i]) for i in range(got.value)]
+
+
+def aov_planes(aov: np.ndarray) -> dict:
+    """Named views of an AOV array [..., AOV_CHANNELS]: hits, t, normal (3), albedo (3),
+    emission (3), matid. Views, not copies; divide the sums by the call's samples per pixel
+    (normal, albedo and t by `hits` for a per-hit mean)."""
+    assert aov.shape[-1] == AOV_CHANNELS
+    return dict(hits=aov[..., AOV_HITS], t=aov[..., AOV_T],
+                normal=aov[..., AOV_NORMAL:AOV_NORMAL + 3],
+                albedo=aov[..., AOV_ALBEDO:AOV_ALBEDO + 3],
+                emission=aov[..., AOV_EMISSION:AOV_EMISSION + 3], matid=aov[..., AOV_MATID])
 
 
 def render_par_lights(blob: Blob, cam: RtCamera, seed: int = 1, device: int = 0,
