@@ -358,6 +358,66 @@ int rt_render_aov(rt_scene* scene, const rt_camera* cam, const rt_render_opts* o
 int rt_render_aov_device(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
                          float* aov_device, void* hip_stream, rt_stats* stats);
 
+/* ---- edge-avoiding a-trous denoiser ---------------------------------------------------------
+ * The first consumer of the AOV guides: the wavelet filter of Dammertz et al. 2010 over a full
+ * contiguous frame. `beauty` is height*width*3 raw sums (what rt_render* writes), `aov` is
+ * height*width*RT_AOV_CHANNELS (what rt_render_aov* writes), `out` is height*width*3 floats in
+ * the scale of the beauty sums (the output stage reads it as it reads the beauty). out may be
+ * the beauty pointer itself (in place); any other overlap is undefined. The buffers need only
+ * 4-byte alignment. Per pixel, with B = beauty_samples and A = aov_samples:
+ *   c = beauty / B; n = normal_sum / hits and z = t_sum / hits (0 where hits == 0; n is not
+ *   renormalised); a = albedo_sum / A; e = emission_sum / A; m = max(a, 1e-3) per channel;
+ *   x0 = (c - e) / m with RT_DENOISE_DEMODULATE, else c.
+ * A pixel whose x0 has a non-finite component is invalid: it is no one's neighbour and its
+ * output is a bitwise copy of its beauty sums. Level k = 0 .. levels-1 steps s = 2^k pixels over
+ * the 5x5 taps q = p + s*(i, j), j outer, i inner; taps outside the frame or on invalid pixels
+ * are skipped; w = h[i]*h[j]*exp(-E), h = (1/16, 1/4, 3/8, 1/4, 1/16), E the sum of the enabled
+ *   colour |x_p - x_q|^2 / (sigma_color * 2^-k)^2      normal |n_p - n_q|^2 / sigma_normal^2
+ *   albedo |a_p - a_q|^2 / sigma_albedo^2
+ *   depth  (z_p - z_q)^2 / (sigma_depth^2 * max(z_p^2, z_q^2, 1e-30))
+ * and x_{k+1}(p) = sum w x_k(q) / sum w. Then y = x*m + e (demodulated) or x, out = y * B.
+ * f32 arithmetic, no atomics, fixed tap order: the same inputs give the same bits on every call.
+ *
+ * A handle owns one device workspace, grown on demand: 48 B per pixel of guides and colour plus,
+ * for levels > 1, the 16 B per pixel the levels alternate with. Calls on one handle are
+ * serialised by a mutex and each call's stream waits for the handle's previous call (an event
+ * wait, whatever stream that was issued on); different handles run concurrently;
+ * rt_denoiser_destroy waits for the handle's work. Null pointers, params and flags are checked
+ * before the handle is read and before any HIP call: width <= 0, height < 0, width*height >=
+ * 2^31, levels outside 1..RT_DENOISE_MAX_LEVELS, non-finite or non-positive sample counts,
+ * non-finite sigmas and unknown flag bits are RT_ERR_INVALID_ARG; height == 0 returns RT_OK and
+ * touches nothing. rt_stats: ms_kernel (events around the call's launches), ms_total, samples =
+ * pixels, launches = kernel launches, out_bytes = bytes written to out; ops all zero. */
+#define RT_DENOISE_MAX_LEVELS 8
+#define RT_DENOISE_DEMODULATE 0x1u   /* filter (beauty - emission) / max(albedo, 1e-3), re-modulate after */
+
+typedef struct rt_denoise_params {   /* 48 bytes, no padding */
+  int32_t width;           /* pixels per row */
+  int32_t height;          /* rows; the buffers are full contiguous frames, top row first */
+  int32_t levels;          /* a-trous levels 1..RT_DENOISE_MAX_LEVELS; level k steps 2^k pixels */
+  uint32_t flags;          /* RT_DENOISE_* ; unknown bits are RT_ERR_INVALID_ARG */
+  double beauty_samples;   /* samples each beauty sum holds (> 0, finite) */
+  double aov_samples;      /* samples each AOV sum holds (> 0, finite) */
+  float sigma_color;       /* edge-stopping widths; <= 0 switches that term off */
+  float sigma_normal;
+  float sigma_depth;
+  float sigma_albedo;
+} rt_denoise_params;
+
+typedef struct rt_denoiser rt_denoiser;   /* opaque: device ordinal + workspace + ordering event */
+
+/* host only: levels 5, RT_DENOISE_DEMODULATE, sigmas 4.0 / 0.3 / 0.1 / 0.1 */
+int  rt_denoise_default_params(int width, int height, double beauty_samples, double aov_samples,
+                               rt_denoise_params* out);
+int  rt_denoiser_create(int device, rt_denoiser** out);
+void rt_denoiser_destroy(rt_denoiser* dn);
+/* asynchronous on hip_stream (may be NULL); stats != NULL synchronises */
+int  rt_denoise_device(rt_denoiser* dn, const rt_denoise_params* p, const float* beauty_dev,
+                       const float* aov_dev, float* out_dev, void* hip_stream, rt_stats* stats);
+/* synchronous, host buffers */
+int  rt_denoise(rt_denoiser* dn, const rt_denoise_params* p, const float* beauty,
+                const float* aov, float* out, rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

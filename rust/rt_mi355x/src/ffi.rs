@@ -62,6 +62,10 @@ pub const RT_AOV_ALBEDO: usize = 5;
 pub const RT_AOV_EMISSION: usize = 8;
 pub const RT_AOV_MATID: usize = 11;
 
+// a-trous denoiser
+pub const RT_DENOISE_MAX_LEVELS: i32 = 8;
+pub const RT_DENOISE_DEMODULATE: u32 = 0x1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -125,13 +129,33 @@ impl Default for rt_stats {
     }
 }
 
-/// Opaque handles (rt_scene, rt_multi).
+/// Parameters of the edge-avoiding a-trous denoiser (rt_denoise*); 48 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_denoise_params {
+    pub width: i32,          // pixels per row
+    pub height: i32,         // rows; full contiguous frames, top row first
+    pub levels: i32,         // 1..RT_DENOISE_MAX_LEVELS; level k steps 2^k pixels
+    pub flags: u32,          // RT_DENOISE_*
+    pub beauty_samples: f64, // samples each beauty sum holds
+    pub aov_samples: f64,    // samples each AOV sum holds
+    pub sigma_color: f32,    // edge-stopping widths; <= 0 switches the term off
+    pub sigma_normal: f32,
+    pub sigma_depth: f32,
+    pub sigma_albedo: f32,
+}
+
+/// Opaque handles (rt_scene, rt_multi, rt_denoiser).
 #[repr(C)]
 pub struct rt_scene {
     _private: [u8; 0],
 }
 #[repr(C)]
 pub struct rt_multi {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct rt_denoiser {
     _private: [u8; 0],
 }
 
@@ -179,4 +203,13 @@ extern "C" {
     pub fn rt_render_aov_device(scene: *mut rt_scene, cam: *const rt_camera,
                                 opts: *const rt_render_opts, aov_device: *mut f32,
                                 hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_denoise_default_params(width: c_int, height: c_int, beauty_samples: f64,
+                                     aov_samples: f64, out: *mut rt_denoise_params) -> c_int;
+    pub fn rt_denoiser_create(device: c_int, out: *mut *mut rt_denoiser) -> c_int;
+    pub fn rt_denoiser_destroy(dn: *mut rt_denoiser);
+    pub fn rt_denoise_device(dn: *mut rt_denoiser, p: *const rt_denoise_params,
+                             beauty_dev: *const f32, aov_dev: *const f32, out_dev: *mut f32,
+                             hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_denoise(dn: *mut rt_denoiser, p: *const rt_denoise_params, beauty: *const f32,
+                      aov: *const f32, out: *mut f32, stats: *mut rt_stats) -> c_int;
 }

@@ -2,11 +2,13 @@
 //
 //   scene selector (main.rs:714-728) -> preset scene (C++ builder, rt_host.h)
 //   -> rt_render (gfx950, rt_mi355x.h)    [render_par_lights, render.rs:144-216]
+//   -> with --denoise: rt_render_aov + rt_denoise (the a-trous filter over the first-hit guides)
 //   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
-//                      [--reference-semantics] [--auto-exposure] [--out file.ppm]
+//                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
+//                      [--out file.ppm]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +41,7 @@ int main(int argc, char** argv) {
   double aspect = 0;
   uint64_t seed = 1, build_seed = 1;
   bool refsem = false, autoexp = false;
+  int denoise_levels = 0;  // 0 = no denoising
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -72,7 +75,11 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = std::atoi(next());
     else if (a == "--reference-semantics") refsem = true;
     else if (a == "--auto-exposure") autoexp = true;
-    else if (a == "--out") out = next();
+    else if (a == "--denoise") {  // the level count is optional
+      denoise_levels = -1;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
+        denoise_levels = std::atoi(argv[++i]);
+    } else if (a == "--out") out = next();
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -104,10 +111,34 @@ int main(int argc, char** argv) {
   o.device = device;
   std::vector<float> accum((size_t)cam.image_width * cam.image_height * 3, 0.f);
   rt_stats st;
-  int rc = rt_render_blob(&blob, &cam, &o, accum.data(), &st);
-  if (rc != RT_OK) {
-    std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error());
-    return 1;
+  int rc;
+  if (!denoise_levels) {
+    rc = rt_render_blob(&blob, &cam, &o, accum.data(), &st);
+    if (rc != RT_OK) {
+      std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error());
+      return 1;
+    }
+  } else {
+    // the beauty render, the first-hit AOVs of the same camera, options and seed, the filter
+    rt_scene* sc = nullptr;
+    rt_denoiser* dn = nullptr;
+    rt_denoise_params dp;
+    std::vector<float> aov((size_t)cam.image_width * cam.image_height * RT_AOV_CHANNELS, 0.f);
+    rt_stats st_aov, st_dn;
+    rc = rt_denoise_default_params(cam.image_width, cam.image_height, cam.samples_per_pixel,
+                                   cam.samples_per_pixel, &dp);
+    if (rc == RT_OK && denoise_levels > 0) dp.levels = denoise_levels;
+    if (rc == RT_OK) rc = rt_scene_create(&blob, device, &sc);
+    if (rc == RT_OK) rc = rt_render(sc, &cam, &o, accum.data(), &st);
+    if (rc == RT_OK) rc = rt_render_aov(sc, &cam, &o, aov.data(), &st_aov);
+    if (rc == RT_OK) rc = rt_denoiser_create(device, &dn);
+    if (rc == RT_OK) rc = rt_denoise(dn, &dp, accum.data(), aov.data(), accum.data(), &st_dn);
+    if (rc != RT_OK) std::fprintf(stderr, "rt_render --denoise: %d %s\n", rc, rt_last_error());
+    rt_denoiser_destroy(dn);
+    rt_scene_destroy(sc);
+    if (rc != RT_OK) return 1;
+    std::fprintf(stderr, "aov %.2f ms, denoise (%d levels) %.3f ms\n", st_aov.ms_kernel, dp.levels,
+                 st_dn.ms_kernel);
   }
   double msps = (double)st.samples / (st.ms_kernel * 1e3);
   std::fprintf(stderr, "kernel %.2f ms, %.1f Msamples/s\n", st.ms_kernel, msps);

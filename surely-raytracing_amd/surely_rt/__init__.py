@@ -43,6 +43,10 @@ AOV_HITS, AOV_T, AOV_NORMAL, AOV_ALBEDO, AOV_EMISSION, AOV_MATID = 0, 1, 2, 5, 8
 AOV_NAMES = ("hits", "t", "nx", "ny", "nz", "albedo_r", "albedo_g", "albedo_b",
              "emission_r", "emission_g", "emission_b", "matid")
 
+# edge-avoiding a-trous denoiser (include/rt_mi355x.h RT_DENOISE_*)
+DENOISE_MAX_LEVELS = 8
+DENOISE_DEMODULATE = 0x1  # filter (beauty - emission) / max(albedo, 1e-3), re-modulate after
+
 OP_NAMES = [
     "samples", "world_queries", "quad_tests", "quad_plane", "quad_interval", "quad_hits",
     "sphere_tests", "sphere_roots", "sphere_hits", "aabb_tests", "translate", "rotate_y",
@@ -86,6 +90,14 @@ class RtStats(C.Structure):
 
     def op_counts(self) -> dict:
         return {n: int(self.ops[i]) for i, n in enumerate(OP_NAMES)}
+
+
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32),
+                ("flags", C.c_uint32), ("beauty_samples", C.c_double),
+                ("aov_samples", C.c_double), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float)]
 
 
 class RtError(RuntimeError):
@@ -193,6 +205,14 @@ def load_device_lib(path: Path) -> C.CDLL:
                                     C.POINTER(RtStats)]),
         "rt_render_aov_device": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
                                            C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_denoise_default_params": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double,
+                                                C.POINTER(RtDenoiseParams)]),
+        "rt_denoiser_create": (C.c_int, [C.c_int, C.POINTER(p)]),
+        "rt_denoiser_destroy": (None, [p]),
+        "rt_denoise_device": (C.c_int, [p, C.POINTER(RtDenoiseParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_denoise": (C.c_int, [p, C.POINTER(RtDenoiseParams), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -528,6 +548,63 @@ def aov_planes(aov: np.ndarray) -> dict:
                 normal=aov[..., AOV_NORMAL:AOV_NORMAL + 3],
                 albedo=aov[..., AOV_ALBEDO:AOV_ALBEDO + 3],
                 emission=aov[..., AOV_EMISSION:AOV_EMISSION + 3], matid=aov[..., AOV_MATID])
+
+
+def denoise_default_params(width: int, height: int, beauty_samples: float,
+                           aov_samples: float | None = None) -> RtDenoiseParams:
+    """rt_denoise_default_params (host only): 5 levels, DENOISE_DEMODULATE, sigmas 4.0 / 0.3 /
+    0.1 / 0.1 for colour / normal / depth / albedo. aov_samples defaults to beauty_samples."""
+    p = RtDenoiseParams()
+    _check_dev(device_lib().rt_denoise_default_params(
+        width, height, beauty_samples, beauty_samples if aov_samples is None else aov_samples,
+        C.byref(p)))
+    return p
+
+
+class Denoiser:
+    """The edge-avoiding a-trous denoiser on one GPU (rt_denoiser_create): a workspace that grows
+    to the largest frame it has seen. Calls on one Denoiser are serialised and ordered; several
+    Denoisers run concurrently."""
+
+    def __init__(self, device: int = 0):
+        self._lib = device_lib()
+        h = C.c_void_p()
+        _check_dev(self._lib.rt_denoiser_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rt_denoiser_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def denoise(self, beauty: np.ndarray, aov: np.ndarray, params: RtDenoiseParams,
+                stats: bool = False):
+        """Synchronous rt_denoise over host arrays: beauty (H, W, 3) raw sums as render()
+        returns them, aov (H, W, AOV_CHANNELS) as render_aov() returns them. Returns the denoised
+        (H, W, 3) float32 frame in the scale of the beauty sums (write_color(out, spp) as for the
+        beauty), or (frame, RtStats) with stats=True."""
+        shape = (params.height, params.width)
+        assert beauty.shape == shape + (3,) and aov.shape == shape + (AOV_CHANNELS,)
+        b = np.ascontiguousarray(beauty, np.float32)
+        a = np.ascontiguousarray(aov, np.float32)
+        out = np.zeros(shape + (3,), np.float32)
+        st = RtStats()
+        _check_dev(self._lib.rt_denoise(self._h, C.byref(params), b.ctypes.data, a.ctypes.data,
+                                        out.ctypes.data, C.byref(st)))
+        return (out, st) if stats else out
+
+    def denoise_device(self, params: RtDenoiseParams, beauty_ptr: int, aov_ptr: int,
+                       out_ptr: int, stream: int = 0, stats: bool = False):
+        """Asynchronous rt_denoise_device over device buffers (out_ptr may equal beauty_ptr)."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_denoise_device(self._h, C.byref(params), C.c_void_p(beauty_ptr),
+                                               C.c_void_p(aov_ptr), C.c_void_p(out_ptr),
+                                               C.c_void_p(stream or None),
+                                               C.byref(st) if st is not None else None))
+        return st
 
 
 def render_par_lights(blob: Blob, cam: RtCamera, seed: int = 1, device: int = 0,
