@@ -4,6 +4,7 @@
 #   build/rt_render_cli    main.rs-equivalent host program (preset -> PPM)
 #   build/librtgather.so   RCCL framebuffer gather for one process per GPU (include/rt_gather.h)
 #   build/rng_key_check    host check of the split stream key (rt_rng.h)
+#   build/librtprobe.so    one C function per device primitive (test infrastructure only)
 #   oracle/_build/*.so     CPU restatement (test infrastructure only)
 PKG      := surely-raytracing_amd
 CSRC     := $(PKG)/csrc
@@ -20,14 +21,15 @@ DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_denoise.hip $(CS
 DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
-.PHONY: all device host oracle cli gather checks clean
-all: device host oracle cli gather checks
+.PHONY: all device host oracle cli gather checks probe clean
+all: device host oracle cli gather checks probe
 
 device: $(BUILD)/librtmi355x.so
 host: $(BUILD)/librthost.so
 cli: $(BUILD)/rt_render_cli
 gather: $(BUILD)/librtgather.so
 checks: $(BUILD)/rng_key_check
+probe: $(BUILD)/librtprobe.so
 oracle: oracle/_build/liboracle_f32.so oracle/_build/liboracle_f64.so oracle/_build/liboracle_f64fma.so
 
 # device headers embedded for the scene-specialised kernels compiled at run time (rt_jit.cpp)
@@ -73,6 +75,12 @@ $(BUILD)/rt_render_cli: $(CSRC)/host/rt_render_cli.cpp $(BUILD)/librthost.so $(B
 $(BUILD)/rng_key_check: $(CSRC)/host/rng_key_check.cpp $(CSRC)/rt_rng.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall $< -o $@
+
+# the device primitives of rt_kernel.h / rt_rng.h behind a C ABI, one by one (tests/probe_lib.py):
+# the product's HIPFLAGS, so each computes the bits it computes in the path kernel; nothing links it
+$(BUILD)/librtprobe.so: $(CSRC)/probe/rt_probe.hip $(JIT_HDR)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -shared $< -o $@
 
 oracle/_build/liboracle_f32.so: oracle/rt_oracle.c include/rt_mi355x.h
 	@mkdir -p oracle/_build

@@ -264,9 +264,12 @@ __device__ __forceinline__ double fma_k(double a, double b) {
 // theta = r*pi/2 (|theta| <= pi/4) evaluated with fused Horner steps: sin = th + th^3 P(th^2)
 // (degree 13), cos = 1 - th^2/2 + th^4 Q(th^2) (degree 14). Relative least-squares fits in 200-bit
 // arithmetic, coefficients rounded to f64 (tools_gpu/fit_sincos.py): measured max error 0.70 ulp
-// (sin) and 0.83 ulp (cos) against the exact values, like the libm result within an ulp, at
-// 15 f64 operations instead of the 40 of an unfused Taylor series; none of the large-argument
-// machinery of the general sincos.
+// (sin) and 0.83 ulp (cos) against the exact sin / cos of the rounded angle theta, like the libm
+// result within an ulp. Against sin / cos of the exact 2 pi u the absolute error reaches 1.2
+// units of 2^-53 (theta's own rounding included), where the reference's f64 libm expression
+// sin(2 pi u) reaches 6 (tests/test_device_math.py, tests/test_device_primitives_gpu.py). 15 f64
+// operations instead of the 40 of an unfused Taylor series; none of the large-argument machinery
+// of the general sincos.
 __device__ __forceinline__ void sincos2pi(double u, double* so, double* co) {
   double t = 4.0 * u;
   double k = floor(t + 0.5);

@@ -1,37 +1,19 @@
 """The device's polynomial transcendentals (rt_kernel.h sincos2pi, log_u01), host-only: the
 coefficients are read from the kernel source and evaluated step by step in f64 with the same
-fused operations (an fma is exact-product-plus-add, rounded once), then compared with the
-exact values (mpmath, 200 bits). Both must stay within an ulp, like the libm results the oracle
-uses (vec3.rs:244 / object.rs:127 phi = 2 pi r1; constant_medium.rs:75 log of a draw)."""
+fused operations (an fma is exact-product-plus-add, rounded once; tests/fmath_emul.py), then
+compared with the exact values (mpmath, 200 bits). Both must stay within an ulp, like the libm
+results the oracle uses (vec3.rs:244 / object.rs:127 phi = 2 pi r1; constant_medium.rs:75 log of a
+draw). tests/test_device_primitives_gpu.py holds the device to the same emulator bit for bit."""
 import math
 import random
-import re
-from pathlib import Path
 
 import mpmath as mp
 import pytest
 
-SRC = (Path(__file__).resolve().parent.parent / "surely-raytracing_amd" / "csrc" /
-       "rt_kernel.h").read_text()
+import fmath_emul as E
+
 mp.mp.prec = 200
-
-
-def _fn(name):
-    i = SRC.index(f"void {name}(" if name == "sincos2pi" else f"double {name}(")
-    return SRC[i:SRC.index("\n}\n", i)]
-
-
-def _hexes(body, var):
-    """The Horner coefficients of `var`, outermost first: the initial literal, then the fma_k
-    constants in order."""
-    first = re.search(rf"double {var} = (-?0x[0-9a-fp.+-]+);", body).group(1)
-    rest = re.findall(rf"{var} = fma_k<__builtin_bit_cast\(uint64_t, \(?(?:double\)\()?"
-                      rf"(-?0x[0-9a-fp.+-]+)\)?\)?>\({var}, \w+\);", body)
-    return [float.fromhex(first)] + [float.fromhex(h) for h in rest]
-
-
-def fma(a, b, c):
-    return float(mp.mpf(a) * mp.mpf(b) + mp.mpf(c))
+_fn, _hexes = E.fn_body, E.hexes
 
 
 def ulps(v, exact):
@@ -40,54 +22,39 @@ def ulps(v, exact):
 
 
 def test_sincos2pi_within_an_ulp():
-    body = _fn("sincos2pi")
-    S, C = _hexes(body, "s"), _hexes(body, "c")
+    S, C = E.sincos_coefficients()
     assert len(S) == 6 and len(C) == 6
     rng = random.Random(5)
     worst = 0.0
     for i in range(1500):
         u = rng.getrandbits(32) * 2.0 ** -32  # a draw: k * 2^-32
-        t = 4.0 * u
-        k = math.floor(t + 0.5)
-        th = (t - k) * (0.5 * math.pi)
-        x2 = th * th
-        s = S[0]
-        for c in S[1:]:
-            s = fma(s, x2, c)
-        s = fma(th * x2, s, th)
-        c = C[0]
-        for cc in C[1:]:
-            c = fma(c, x2, cc)
-        c = fma(fma(c, x2, -0.5), x2, 1.0)
+        _, th, s, c = E.sincos2pi_core(u)
         if th != 0.0:
             worst = max(worst, ulps(s, mp.sin(mp.mpf(th))))
         worst = max(worst, ulps(c, mp.cos(mp.mpf(th))))
     assert worst < 1.0, worst
 
 
+def test_sincos2pi_absolute_error_no_worse_than_the_reference_expression():
+    """Against sin / cos of the exact 2 pi u (not of the rounded angle th): the whole function,
+    quadrant logic included, errs no more than the reference's f64 libm expression does on the
+    same draws (the rounding of 2 pi u alone costs that expression several units)."""
+    rng = random.Random(5)
+    us = [k * 2.0 ** -32 for k in E.sincos_boundary_ks() + [rng.getrandbits(32) for _ in range(4000)]]
+    ds, dc, ls, lc = E.sincos_abs_errors(us, [E.sincos2pi(u) for u in us])
+    print(f"sincos2pi emulator |err| / 2^-53: sin {ds:.3f} cos {dc:.3f}; libm expression: "
+          f"sin {ls:.3f} cos {lc:.3f}")
+    assert ds <= ls and dc <= lc, (ds, dc, ls, lc)
+
+
 def test_log_u01_within_an_ulp_and_log0():
     body = _fn("log_u01")
-    R = _hexes(body, "r")
+    R, ln2_lo, ln2_hi = E.log_coefficients()
     assert len(R) == 7
-    ln2_lo = float.fromhex(re.search(r"dk \* (0x[0-9a-fp.+-]+)\);  // ln2_lo", body).group(1))
-    ln2_hi = float.fromhex(re.search(r"dk \* (0x[0-9a-fp.+-]+) - ", body).group(1))
+    assert 0.0 < ln2_lo < 2.0 ** -25 and ln2_hi + ln2_lo == math.log(2.0)
     assert "x == 0.0 ? -kInf" in body  # log(0) = -inf: the reference's infinite free path
 
-    def flog(x):
-        m, e = math.frexp(x)
-        if m < 0.7071067811865476:
-            m, e = m * 2.0, e - 1
-        f = m - 1.0
-        hfsq = 0.5 * f * f
-        s = float(mp.mpf(f) / mp.mpf(2.0 + f))  # div_nr: the IEEE quotient within an ulp
-        z = s * s
-        r = R[0]
-        for c in R[1:]:
-            r = fma(r, z, c)
-        dk = float(e)
-        t = fma(s, hfsq + r * z, dk * ln2_lo)
-        return dk * ln2_hi - ((hfsq - t) - f)
-
+    flog = E.log_u01
     rng = random.Random(7)
     ks = [1, 2, 3, 2 ** 31, 2 ** 32 - 1, 0x5A827999] + [rng.getrandbits(32) for _ in range(1500)]
     worst = max(ulps(flog(k * 2.0 ** -32), mp.log(mp.mpf(k) * mp.mpf(2) ** -32))
