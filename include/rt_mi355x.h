@@ -418,6 +418,86 @@ int  rt_denoise_device(rt_denoiser* dn, const rt_denoise_params* p, const float*
 int  rt_denoise(rt_denoiser* dn, const rt_denoise_params* p, const float* beauty,
                 const float* aov, float* out, rt_stats* stats);
 
+/* ---- per-pixel sample moments ----------------------------------------------------------------
+ * rt_render_device plus the second moment of what it sums. accum_rgb is exactly what
+ * rt_render_device writes for the same arguments, bit for bit. m2_rgb holds n_rows * W * 3 floats:
+ * per pixel and channel Q = sum_j R_j^2 over the call's stratum rows s_j in s_j order, R_j being
+ * the f64 total of row s_j's samples that the reduction adds into the running sum (whatever item
+ * kinds the launch split the row into); each step is q = fma(R, R, q) in f64 and the result is
+ * rounded once to f32. RT_FLAG_OVERWRITE governs both buffers: without it each m2 value becomes
+ * (float)((double)old + q), as for accum, so calls over disjoint sj ranges compose into the sums
+ * of the whole frame. A non-finite row total gives the non-finite Q of IEEE arithmetic. Flags,
+ * limits, status codes, re-entrancy, slots and the split of tall row ranges are those of
+ * rt_render_device; a null m2 pointer is RT_ERR_INVALID_ARG; n_rows == 0 returns RT_OK and touches
+ * nothing; rt_stats as rt_render_device fills it. A render that runs as several stratum-row chunks
+ * carries Q in a second f64 buffer of its render slot (24 B per pixel, allocated by the slot's
+ * first such render).
+ *
+ * The estimator the pair supports: with n stratum rows held (n >= 2), B samples held and S the
+ * beauty sum,
+ *   Var(mean) ~= max(0, Q - S^2 / n) * n / ((n - 1) * B^2),
+ * the between-row estimate of the variance of the pixel mean S / B (slightly conservative under
+ * stratification: the rows are not identically distributed). */
+int rt_render_moments_device(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                             float* accum_rgb_device, float* m2_rgb_device, void* hip_stream,
+                             rt_stats* stats);
+/* synchronous, host buffers */
+int rt_render_moments(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                      float* accum_rgb, float* m2_rgb, rt_stats* stats);
+
+/* ---- variance-guided a-trous denoiser ---------------------------------------------------------
+ * rt_denoise with the colour distance normalised by a per-pixel variance estimate that is
+ * propagated through the levels (Dammertz et al. with the variance guidance of SVGF, Schied et al.
+ * 2017). Everything said of rt_denoise_device holds: c, n, z, a, e, m, x0, invalid pixels and
+ * their bitwise pass-through, taps and their order, skipped taps, the normal, albedo and depth
+ * terms, re-modulation, out == beauty, 4-byte alignment, handle serialisation, stream order, the
+ * argument checks (made before the handle is read and before any HIP call). The differences:
+ *   m2      height*width*3 floats as rt_render_moments* writes them, over the same
+ *           beauty_rows = n stratum rows as the beauty sums S.
+ *   var_c   = max(0, Q_c - S_c^2 / n) * n / ((n - 1) * B^2) per channel, evaluated in f64 from the
+ *           f32 inputs; v_raw = sum_c var_c / m_c^2 (demodulating) or sum_c var_c, rounded to f32.
+ *           A pixel whose Q (or v_raw) has a non-finite component is invalid, like one with a
+ *           non-finite x0.
+ *   v_0(p)  = sum g v_raw(q) / sum g over the valid in-frame pixels q of the 3x3 block around p,
+ *           g = (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), j outer, i inner.
+ *   colour  term of level k: |x_p - x_q|^2 / (sigma_color^2 * (v_k(p) + v_k(q) + 1e-10)); no
+ *           2^-k factor, the propagated variance takes its place.
+ *   v_{k+1}(p) = sum w^2 v_k(q) / (sum w)^2 over the taps and weights that form x_{k+1}(p).
+ *   var_out (may be NULL) height*width floats: v_levels(p), the variance of the filtered value in
+ *           filter space (demodulated when that flag is set); 0 for invalid pixels. The quantity
+ *           an adaptive sampler would threshold.
+ * Also RT_ERR_INVALID_ARG: beauty_rows < 2, _pad0 != 0, a null m2. The workspace of a handle that
+ * has run this mode is 64 B per pixel whatever the level count (the prefilter writes the second
+ * colour record). rt_stats: launches = kernel launches (2 + levels), out_bytes = bytes written to
+ * out and var_out. */
+typedef struct rt_denoise_var_params {   /* 56 bytes, no padding */
+  int32_t width;           /* as rt_denoise_params */
+  int32_t height;
+  int32_t levels;
+  uint32_t flags;          /* RT_DENOISE_DEMODULATE only */
+  double beauty_samples;
+  double aov_samples;
+  int32_t beauty_rows;     /* stratum rows the beauty and m2 sums hold, >= 2 */
+  int32_t _pad0;           /* must be 0 */
+  float sigma_color;       /* in units of the pair's standard deviation; <= 0 switches the term off */
+  float sigma_normal;
+  float sigma_depth;
+  float sigma_albedo;
+} rt_denoise_var_params;
+
+/* host only: levels 5, RT_DENOISE_DEMODULATE, sigmas 4.0 / 0.3 / 0.1 / 0.1 (sigma_color: the best
+ * of 0.5, 1, 2, 4 on cornell_box at 4 and at 16 spp) */
+int  rt_denoise_var_default_params(int width, int height, double beauty_samples, int beauty_rows,
+                                   double aov_samples, rt_denoise_var_params* out);
+/* asynchronous on hip_stream (may be NULL); stats != NULL synchronises */
+int  rt_denoise_var_device(rt_denoiser* dn, const rt_denoise_var_params* p,
+                           const float* beauty_dev, const float* m2_dev, const float* aov_dev,
+                           float* out_dev, float* var_out_dev, void* hip_stream, rt_stats* stats);
+/* synchronous, host buffers */
+int  rt_denoise_var(rt_denoiser* dn, const rt_denoise_var_params* p, const float* beauty,
+                    const float* m2, const float* aov, float* out, float* var_out,
+                    rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,24 @@ pub struct rt_denoise_params {
     pub sigma_albedo: f32,
 }
 
+/// Parameters of the variance-guided a-trous denoiser (rt_denoise_var*); 56 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_denoise_var_params {
+    pub width: i32,
+    pub height: i32,
+    pub levels: i32,
+    pub flags: u32,          // RT_DENOISE_DEMODULATE only
+    pub beauty_samples: f64,
+    pub aov_samples: f64,
+    pub beauty_rows: i32,    // stratum rows the beauty and m2 sums hold, >= 2
+    pub _pad0: i32,          // must be 0
+    pub sigma_color: f32,    // in units of the pair's standard deviation; <= 0: term off
+    pub sigma_normal: f32,
+    pub sigma_depth: f32,
+    pub sigma_albedo: f32,
+}
+
 /// Opaque handles (rt_scene, rt_multi, rt_denoiser).
 #[repr(C)]
 pub struct rt_scene {
@@ -212,4 +230,21 @@ extern "C" {
                              hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_denoise(dn: *mut rt_denoiser, p: *const rt_denoise_params, beauty: *const f32,
                       aov: *const f32, out: *mut f32, stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_moments_device(scene: *mut rt_scene, cam: *const rt_camera,
+                                    opts: *const rt_render_opts, accum_rgb_device: *mut f32,
+                                    m2_rgb_device: *mut f32, hip_stream: *mut c_void,
+                                    stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_moments(scene: *mut rt_scene, cam: *const rt_camera,
+                             opts: *const rt_render_opts, accum_rgb: *mut f32, m2_rgb: *mut f32,
+                             stats: *mut rt_stats) -> c_int;
+    pub fn rt_denoise_var_default_params(width: c_int, height: c_int, beauty_samples: f64,
+                                         beauty_rows: c_int, aov_samples: f64,
+                                         out: *mut rt_denoise_var_params) -> c_int;
+    pub fn rt_denoise_var_device(dn: *mut rt_denoiser, p: *const rt_denoise_var_params,
+                                 beauty_dev: *const f32, m2_dev: *const f32,
+                                 aov_dev: *const f32, out_dev: *mut f32, var_out_dev: *mut f32,
+                                 hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_denoise_var(dn: *mut rt_denoiser, p: *const rt_denoise_var_params,
+                          beauty: *const f32, m2: *const f32, aov: *const f32, out: *mut f32,
+                          var_out: *mut f32, stats: *mut rt_stats) -> c_int;
 }

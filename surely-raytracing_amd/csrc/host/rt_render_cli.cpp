@@ -3,12 +3,14 @@
 //   scene selector (main.rs:714-728) -> preset scene (C++ builder, rt_host.h)
 //   -> rt_render (gfx950, rt_mi355x.h)    [render_par_lights, render.rs:144-216]
 //   -> with --denoise: rt_render_aov + rt_denoise (the a-trous filter over the first-hit guides)
+//   -> with --denoise-var: rt_render_moments + rt_render_aov + rt_denoise_var (the same filter
+//      guided by the per-pixel variance of the row totals; needs spp >= 4)
 //   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
-//                      [--out file.ppm]
+//                      [--denoise-var [levels]] [--out file.ppm]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
   uint64_t seed = 1, build_seed = 1;
   bool refsem = false, autoexp = false;
   int denoise_levels = 0;  // 0 = no denoising
+  bool denoise_var = false;  // the variance-guided filter instead of the plain one
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -75,7 +78,8 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = std::atoi(next());
     else if (a == "--reference-semantics") refsem = true;
     else if (a == "--auto-exposure") autoexp = true;
-    else if (a == "--denoise") {  // the level count is optional
+    else if (a == "--denoise" || a == "--denoise-var") {  // the level count is optional
+      denoise_var = a == "--denoise-var";
       denoise_levels = -1;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
         denoise_levels = std::atoi(argv[++i]);
@@ -118,6 +122,30 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error());
       return 1;
     }
+  } else if (denoise_var) {
+    // the moments render, the first-hit AOVs of the same camera, options and seed, the filter
+    rt_scene* sc = nullptr;
+    rt_denoiser* dn = nullptr;
+    rt_denoise_var_params dp;
+    std::vector<float> m2(accum.size(), 0.f);
+    std::vector<float> aov((size_t)cam.image_width * cam.image_height * RT_AOV_CHANNELS, 0.f);
+    rt_stats st_aov, st_dn;
+    rc = rt_denoise_var_default_params(cam.image_width, cam.image_height, cam.samples_per_pixel,
+                                       cam.sqrt_spp, cam.samples_per_pixel, &dp);
+    if (rc == RT_OK && denoise_levels > 0) dp.levels = denoise_levels;
+    if (rc == RT_OK) rc = rt_scene_create(&blob, device, &sc);
+    if (rc == RT_OK) rc = rt_render_moments(sc, &cam, &o, accum.data(), m2.data(), &st);
+    if (rc == RT_OK) rc = rt_render_aov(sc, &cam, &o, aov.data(), &st_aov);
+    if (rc == RT_OK) rc = rt_denoiser_create(device, &dn);
+    if (rc == RT_OK)
+      rc = rt_denoise_var(dn, &dp, accum.data(), m2.data(), aov.data(), accum.data(), nullptr,
+                          &st_dn);
+    if (rc != RT_OK) std::fprintf(stderr, "rt_render --denoise-var: %d %s\n", rc, rt_last_error());
+    rt_denoiser_destroy(dn);
+    rt_scene_destroy(sc);
+    if (rc != RT_OK) return 1;
+    std::fprintf(stderr, "aov %.2f ms, variance-guided denoise (%d levels) %.3f ms\n",
+                 st_aov.ms_kernel, dp.levels, st_dn.ms_kernel);
   } else {
     // the beauty render, the first-hit AOVs of the same camera, options and seed, the filter
     rt_scene* sc = nullptr;

@@ -63,12 +63,26 @@ __global__ __launch_bounds__(BlockOf<BVH>::value, (MinWaves<VOL, TEX, BVH>::valu
 // row, segment and tail items. One wave per 8x8 tile, lane = pixel of the tile: each load
 // instruction reads 64 * 8 contiguous bytes. Chunked calls carry the running total in `tot`.
 // mode: bit0 first chunk, bit1 last chunk (write accum), bit2 overwrite.
+//
+// M2 (rt_render_moments*): beside the running total, q = fma(R, R, q) per channel over the same
+// row totals R in the same order: the pixel's second moment over the call's stratum rows, carried
+// between chunks in `mo.tot2` and written to `mo.m2` exactly as the total is to `accum`. The plain
+// instantiation (MomentsOut<false>, an empty argument) names none of it.
 constexpr int kRedU = 8;  // values loaded ahead per step of rt_reduce
+template <bool M2>
+struct MomentsOut {};  // the plain reduction: no further kernel argument
+template <>
+struct MomentsOut<true> {
+  double* tot2;  // the chunks' carry of q
+  float* m2;     // the caller's second buffer
+};
+template <bool M2>
 __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part,
                                                  double* __restrict__ tot,
                                                  float* __restrict__ accum, int W, int n_rows,
                                                  int tiles_x, int n_tiles, int n_sj, int S,
-                                                 int n_pairs_r, int n_pairs_a, int mode) {
+                                                 int n_pairs_r, int n_pairs_a, int mode,
+                                                 MomentsOut<M2> mo) {
   const int tile_id = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   const int pv = threadIdx.x & 63;
   if (tile_id >= n_tiles) return;
@@ -84,6 +98,14 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
     t0 = tot[3 * i];
     t1 = tot[3 * i + 1];
     t2 = tot[3 * i + 2];
+  }
+  double m0 = 0.0, m1 = 0.0, m2c = 0.0;  // M2: sum of R^2
+  if constexpr (M2) {
+    if (!(mode & 1)) {
+      m0 = mo.tot2[3 * i];
+      m1 = mo.tot2[3 * i + 1];
+      m2c = mo.tot2[3 * i + 2];
+    }
   }
   const int q0 = tile_id * n_sj;  // this tile's pairs q0 .. q0 + n_sj - 1 (s_j order)
   const int k_r = max(0, min(n_sj, n_pairs_r - q0)), k_a = max(0, min(n_sj, n_pairs_a - q0));
@@ -101,10 +123,19 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
       }
 #pragma unroll
       for (int u = 0; u < kRedU; ++u) t0 += v[u][0], t1 += v[u][1], t2 += v[u][2];
+      if (M2) {
+#pragma unroll
+        for (int u = 0; u < kRedU; ++u) {
+          m0 = fma(v[u][0], v[u][0], m0);
+          m1 = fma(v[u][1], v[u][1], m1);
+          m2c = fma(v[u][2], v[u][2], m2c);
+        }
+      }
     }
     for (; k < k_r; ++k) {
       const double* e = r + (size_t)k * 192;
       t0 += e[0], t1 += e[1], t2 += e[2];
+      if (M2) m0 = fma(e[0], e[0], m0), m1 = fma(e[1], e[1], m1), m2c = fma(e[2], e[2], m2c);
     }
   }
   // segment pairs: the row total of n_blk block partials
@@ -129,6 +160,7 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
       r0 += e[0], r1 += e[1], r2 += e[2];
     }
     t0 += r0, t1 += r1, t2 += r2;
+    if (M2) m0 = fma(r0, r0, m0), m1 = fma(r1, r1, m1), m2c = fma(r2, r2, m2c);
   }
   // tail pairs: per-sample values, summed per block of kPoolSi samples, then the blocks
   const size_t tail0 = (size_t)n_pairs_r + (size_t)(n_pairs_a - n_pairs_r) * n_blk;
@@ -157,6 +189,7 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
       }
     }
     t0 += R0, t1 += R1, t2 += R2;
+    if (M2) m0 = fma(R0, R0, m0), m1 = fma(R1, R1, m1), m2c = fma(R2, R2, m2c);
   }
   float* a = accum + 3 * i;
   if (mode & 2) {
@@ -168,6 +201,19 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
     }
   } else {
     tot[3 * i] = t0, tot[3 * i + 1] = t1, tot[3 * i + 2] = t2;
+  }
+  if constexpr (M2) {
+    float* b = mo.m2 + 3 * i;
+    if (mode & 2) {
+      if (mode & 4) {
+        b[0] = (float)m0, b[1] = (float)m1, b[2] = (float)m2c;
+      } else {
+        b[0] = (float)((double)b[0] + m0), b[1] = (float)((double)b[1] + m1);
+        b[2] = (float)((double)b[2] + m2c);
+      }
+    } else {
+      mo.tot2[3 * i] = m0, mo.tot2[3 * i + 1] = m1, mo.tot2[3 * i + 2] = m2c;
+    }
   }
 }
 
@@ -466,6 +512,7 @@ void rt_scene_destroy(rt_scene* sc) {
   if (sc->dev) (void)hipFree(sc->dev);
   for (const auto& sl : sc->slots) {
     if (sl->work) (void)hipFree(sl->work);
+    if (sl->work2) (void)hipFree(sl->work2);
     if (sl->ops) (void)hipFree(sl->ops);
     if (sl->done) (void)hipEventDestroy(sl->done);
     if (sl->ev0) (void)hipEventDestroy(sl->ev0);
@@ -578,8 +625,10 @@ int rts::acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStrea
   }
 }
 
+// m2 != nullptr: a moments render (rt_render_moments_device), which also writes the second
+// moments of the row totals; every other step is the plain render's.
 static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
-                              float* accum, void* stream_v, rt_stats* stats) {
+                              float* accum, float* m2, void* stream_v, rt_stats* stats) {
   auto t0 = std::chrono::steady_clock::now();
   if (!sc || !cam || !opts || !accum) return set_err(RT_ERR_INVALID_ARG, "null argument");
   const int W = cam->image_width, S = cam->sqrt_spp;
@@ -868,7 +917,18 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     HIP_TRY(hipMalloc(&sl->work, need));
     sl->work_bytes = need;
   }
+  // a moments render in several chunks carries its second moments in a buffer of the slot's own,
+  // allocated by the first such render (plain renders never pay for it)
+  if (m2 && chunk < n_sj && tot_bytes > sl->work2_bytes) {
+    if (sl->recorded) HIP_TRY(hipEventSynchronize(sl->done));
+    if (sl->work2) HIP_TRY(hipFree(sl->work2));
+    sl->work2 = nullptr;
+    sl->work2_bytes = 0;
+    HIP_TRY(hipMalloc(&sl->work2, tot_bytes));
+    sl->work2_bytes = tot_bytes;
+  }
   double* tot = (double*)sl->work;
+  double* tot2 = (double*)sl->work2;  // read and written only between chunks
   P.part = (double*)(sl->work + tot_bytes);
   hold.stream = stream;
   hold.enqueued = true;  // from here on a failure still records `done` (SlotHold)
@@ -907,9 +967,15 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     ++sc->n_tev;
     const int mode = (c0 == sj0 ? 1 : 0) | (c0 + cn == sj0 + n_sj ? 2 : 0) |
                      ((opts->flags & RT_FLAG_OVERWRITE) ? 4 : 0);
-    hipLaunchKernelGGL(rt_reduce, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, P.part,
-                       tot, accum, W, opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r,
-                       P.n_pairs_a, mode);
+    const dim3 rgrid((unsigned)((n_tiles + 3) / 4));
+    if (m2)
+      hipLaunchKernelGGL(rt_reduce<true>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
+                         opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
+                         MomentsOut<true>{tot2, m2});
+    else
+      hipLaunchKernelGGL(rt_reduce<false>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
+                         opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
+                         MomentsOut<false>{});
     HIP_TRY(hipGetLastError());
   }
   ++sc->n_render;
@@ -938,21 +1004,20 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   return RT_OK;
 }
 
-extern "C" {
-
-int rt_render_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
-                     float* accum, void* stream_v, rt_stats* stats) {
-  if (!sc || !cam || !opts || !accum) return set_err(RT_ERR_INVALID_ARG, "null argument");
+// rt_render_device and rt_render_moments_device (m2 != nullptr): tall row ranges as sub-calls
+static int render_device_split(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
+                               float* accum, float* m2, void* stream_v, rt_stats* stats) {
   if (opts->n_rows <= kRowsPerCall || cam->image_width <= 0)
-    return render_device_rows(sc, cam, opts, accum, stream_v, stats);
+    return render_device_rows(sc, cam, opts, accum, m2, stream_v, stats);
   auto t0 = std::chrono::steady_clock::now();
   rt_stats part{}, sum{};
   for (int k0 = 0; k0 < opts->n_rows; k0 += kRowsPerCall) {
     rt_render_opts o = *opts;
     o.row_begin = opts->row_begin + k0 * opts->row_step;
     o.n_rows = std::min(kRowsPerCall, opts->n_rows - k0);
-    const int rc = render_device_rows(sc, cam, &o, accum + (size_t)k0 * cam->image_width * 3,
-                                      stream_v, stats ? &part : nullptr);
+    const size_t off = (size_t)k0 * cam->image_width * 3;
+    const int rc = render_device_rows(sc, cam, &o, accum + off, m2 ? m2 + off : nullptr, stream_v,
+                                      stats ? &part : nullptr);
     if (rc != RT_OK) return rc;
     if (stats) {
       sum.ms_kernel += part.ms_kernel;
@@ -968,6 +1033,20 @@ int rt_render_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* o
     *stats = sum;
   }
   return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
+                     float* accum, void* stream_v, rt_stats* stats) {
+  if (!sc || !cam || !opts || !accum) return set_err(RT_ERR_INVALID_ARG, "null argument");
+  return render_device_split(sc, cam, opts, accum, nullptr, stream_v, stats);
+}
+
+int rt_render_moments_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
+                             float* accum, float* m2, void* stream_v, rt_stats* stats) {
+  if (!sc || !cam || !opts || !accum || !m2) return set_err(RT_ERR_INVALID_ARG, "null argument");
+  return render_device_split(sc, cam, opts, accum, m2, stream_v, stats);
 }
 
 // Profiling builds (-DRT_PROF, not shipped): the ordered-BVH walk counters of the last render
@@ -1033,6 +1112,42 @@ int rt_render(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts, fl
   int rc = rt_render_device(sc, cam, opts, d, nullptr, stats ? stats : &local);
   if (rc == RT_OK) {
     e = hipMemcpy(accum, d, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download accum: ") + hipGetErrorString(e));
+  }
+  (void)hipFree(d);
+  if (rc == RT_OK && stats)
+    stats->ms_total =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int rt_render_moments(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts, float* accum,
+                      float* m2, rt_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!sc || !cam || !opts || !accum || !m2) return set_err(RT_ERR_INVALID_ARG, "null argument");
+  if (opts->n_rows < 0 || cam->image_width <= 0) return set_err(RT_ERR_INVALID_ARG, "bad size");
+  HIP_TRY(hipSetDevice(sc->device));
+  const size_t bytes = (size_t)opts->n_rows * cam->image_width * 3 * sizeof(float);
+  if (bytes == 0) return RT_OK;
+  // one allocation: the beauty sums, then the second moments
+  uint8_t* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, 2 * bytes));
+  float* const d_acc = reinterpret_cast<float*>(d);
+  float* const d_m2 = reinterpret_cast<float*>(d + bytes);
+  hipError_t e = hipSuccess;
+  if (!(opts->flags & RT_FLAG_OVERWRITE)) {
+    e = hipMemcpy(d_acc, accum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_m2, m2, bytes, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return set_err(RT_ERR_HIP, std::string("upload accum: ") + hipGetErrorString(e));
+  }
+  rt_stats local;
+  int rc = rt_render_moments_device(sc, cam, opts, d_acc, d_m2, nullptr, stats ? stats : &local);
+  if (rc == RT_OK) {
+    e = hipMemcpy(accum, d_acc, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(m2, d_m2, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download accum: ") + hipGetErrorString(e));
   }
   (void)hipFree(d);

@@ -59,6 +59,8 @@ RTS_HIDDEN LdsPlan plan_lds(const rtl_scene_header& hdr, uint32_t o_perl, uint32
 struct RenderSlot {
   uint8_t* work = nullptr;  // row totals / segment partials / tail samples + f64 running sums
   size_t work_bytes = 0;
+  uint8_t* work2 = nullptr;  // moments renders in several chunks: the f64 running sums of R^2
+  size_t work2_bytes = 0;
   unsigned long long* ops = nullptr;  // 32 op counters, the pool-queue word (32), profiling (40..)
   unsigned int* queue = nullptr;
   hipEvent_t done = nullptr;  // recorded after the render's last kernel

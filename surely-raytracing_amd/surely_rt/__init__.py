@@ -100,6 +100,14 @@ class RtDenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float)]
 
 
+class RtDenoiseVarParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32),
+                ("flags", C.c_uint32), ("beauty_samples", C.c_double),
+                ("aov_samples", C.c_double), ("beauty_rows", C.c_int32), ("_pad0", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rt error {code}: {msg}")
@@ -213,6 +221,18 @@ def load_device_lib(path: Path) -> C.CDLL:
                                         C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
         "rt_denoise": (C.c_int, [p, C.POINTER(RtDenoiseParams), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_moments": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
+                                        C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_moments_device": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
+                                               C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(RtStats)]),
+        "rt_denoise_var_default_params": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int,
+                                                    C.c_double, C.POINTER(RtDenoiseVarParams)]),
+        "rt_denoise_var_device": (C.c_int, [p, C.POINTER(RtDenoiseVarParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(RtStats)]),
+        "rt_denoise_var": (C.c_int, [p, C.POINTER(RtDenoiseVarParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -499,6 +519,36 @@ class DeviceScene:
                                               C.byref(st) if st is not None else None))
         return st
 
+    def render_moments(self, cam: RtCamera, opts: RtRenderOpts, accum: np.ndarray | None = None,
+                       m2: np.ndarray | None = None, stats: bool = False):
+        """Synchronous rt_render_moments into host float32 (n_rows, W, 3) arrays: the beauty sums
+        exactly as render() gives them, and per pixel and channel the sum over the call's stratum
+        rows of the squared row totals. Without RT_FLAG_OVERWRITE both are added into the arrays
+        passed in. Returns (accum, m2), or (accum, m2, stats) with stats=True. With n rows and B
+        samples held, max(0, m2 - accum**2 / n) * n / ((n - 1) * B**2) estimates the variance of
+        the pixel mean."""
+        shape = (opts.n_rows, cam.image_width, 3)
+        if accum is None:
+            accum = np.zeros(shape, np.float32)
+        if m2 is None:
+            m2 = np.zeros(shape, np.float32)
+        for a in (accum, m2):
+            assert a.shape == shape and a.dtype == np.float32 and a.flags.c_contiguous
+        st = RtStats()
+        _check_dev(self._lib.rt_render_moments(self._h, C.byref(cam), C.byref(opts),
+                                               accum.ctypes.data, m2.ctypes.data, C.byref(st)))
+        return (accum, m2, st) if stats else (accum, m2)
+
+    def render_moments_device(self, cam: RtCamera, opts: RtRenderOpts, accum_ptr: int,
+                              m2_ptr: int, stream: int = 0, stats: bool = False):
+        """Asynchronous rt_render_moments_device into two device buffers of n_rows * W * 3
+        floats."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_render_moments_device(
+            self._h, C.byref(cam), C.byref(opts), C.c_void_p(accum_ptr), C.c_void_p(m2_ptr),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
+        return st
+
     def render_aov(self, cam: RtCamera, opts: RtRenderOpts, aov: np.ndarray | None = None):
         """Synchronous first-hit AOV pass (rt_render_aov) into a host float32
         (n_rows, W, AOV_CHANNELS) array: per-pixel sums over the call's samples of hits, t (the
@@ -561,6 +611,18 @@ def denoise_default_params(width: int, height: int, beauty_samples: float,
     return p
 
 
+def denoise_var_default_params(width: int, height: int, beauty_samples: float, beauty_rows: int,
+                               aov_samples: float | None = None) -> RtDenoiseVarParams:
+    """rt_denoise_var_default_params (host only): 5 levels, DENOISE_DEMODULATE, sigmas 4.0 / 0.3 /
+    0.1 / 0.1; sigma_color is in units of a pixel pair's standard deviation. beauty_rows: the
+    stratum rows the beauty and m2 sums hold (cam.sqrt_spp for a whole render)."""
+    p = RtDenoiseVarParams()
+    _check_dev(device_lib().rt_denoise_var_default_params(
+        width, height, beauty_samples, beauty_rows,
+        beauty_samples if aov_samples is None else aov_samples, C.byref(p)))
+    return p
+
+
 class Denoiser:
     """The edge-avoiding a-trous denoiser on one GPU (rt_denoiser_create): a workspace that grows
     to the largest frame it has seen. Calls on one Denoiser are serialised and ordered; several
@@ -604,6 +666,40 @@ class Denoiser:
                                                C.c_void_p(aov_ptr), C.c_void_p(out_ptr),
                                                C.c_void_p(stream or None),
                                                C.byref(st) if st is not None else None))
+        return st
+
+
+    def denoise_var(self, beauty: np.ndarray, m2: np.ndarray, aov: np.ndarray,
+                    params: RtDenoiseVarParams, var_out: bool = False, stats: bool = False):
+        """Synchronous rt_denoise_var over host arrays: beauty and m2 (H, W, 3) as
+        render_moments() returns them, aov as render_aov() returns it. Returns the denoised frame,
+        followed by the (H, W) variance of the filtered value with var_out=True and by RtStats
+        with stats=True."""
+        shape = (params.height, params.width)
+        assert beauty.shape == shape + (3,) and m2.shape == shape + (3,)
+        assert aov.shape == shape + (AOV_CHANNELS,)
+        b = np.ascontiguousarray(beauty, np.float32)
+        q = np.ascontiguousarray(m2, np.float32)
+        a = np.ascontiguousarray(aov, np.float32)
+        out = np.zeros(shape + (3,), np.float32)
+        var = np.zeros(shape, np.float32) if var_out else None
+        st = RtStats()
+        _check_dev(self._lib.rt_denoise_var(self._h, C.byref(params), b.ctypes.data,
+                                            q.ctypes.data, a.ctypes.data, out.ctypes.data,
+                                            var.ctypes.data if var_out else None, C.byref(st)))
+        res = (out,) + ((var,) if var_out else ()) + ((st,) if stats else ())
+        return res if len(res) > 1 else out
+
+    def denoise_var_device(self, params: RtDenoiseVarParams, beauty_ptr: int, m2_ptr: int,
+                           aov_ptr: int, out_ptr: int, var_out_ptr: int = 0, stream: int = 0,
+                           stats: bool = False):
+        """Asynchronous rt_denoise_var_device over device buffers (out_ptr may equal beauty_ptr;
+        var_out_ptr 0 = no variance output)."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_denoise_var_device(
+            self._h, C.byref(params), C.c_void_p(beauty_ptr), C.c_void_p(m2_ptr),
+            C.c_void_p(aov_ptr), C.c_void_p(out_ptr), C.c_void_p(var_out_ptr or None),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
 
 
