@@ -4,7 +4,7 @@
 #   build/rt_render_cli    main.rs-equivalent host program (preset -> PPM)
 #   build/librtgather.so   RCCL framebuffer gather for one process per GPU (include/rt_gather.h)
 #   build/rng_key_check    host check of the split stream key (rt_rng.h)
-#   build/librtprobe.so    one C function per device primitive (test infrastructure only)
+#   build/librtprobe.so    one C function per device primitive and scene function (test infrastructure only)
 #   oracle/_build/*.so     CPU restatement (test infrastructure only)
 PKG      := surely-raytracing_amd
 CSRC     := $(PKG)/csrc
@@ -76,11 +76,12 @@ $(BUILD)/rng_key_check: $(CSRC)/host/rng_key_check.cpp $(CSRC)/rt_rng.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall $< -o $@
 
-# the device primitives of rt_kernel.h / rt_rng.h behind a C ABI, one by one (tests/probe_lib.py):
-# the product's HIPFLAGS, so each computes the bits it computes in the path kernel; nothing links it
-$(BUILD)/librtprobe.so: $(CSRC)/probe/rt_probe.hip $(JIT_HDR)
+# the device primitives of rt_kernel.h / rt_rng.h behind a C ABI, one by one, and the scene-level
+# functions on a flattened scene (tests/probe_lib.py): the product's HIPFLAGS, so each computes the
+# bits it computes in the path kernel, and the product's flattener; nothing links it
+$(BUILD)/librtprobe.so: $(CSRC)/probe/rt_probe.hip $(CSRC)/probe/rt_probe_scene.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(JIT_HDR) $(CSRC)/rt_flatten.hpp
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -shared $< -o $@
+	$(HIPCC) $(HIPFLAGS) -shared $(filter %.hip %.cpp,$^) -o $@
 
 oracle/_build/liboracle_f32.so: oracle/rt_oracle.c include/rt_mi355x.h
 	@mkdir -p oracle/_build

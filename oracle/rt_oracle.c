@@ -527,6 +527,7 @@ typedef struct {
   vec3 p, normal;
   real t, u, v;
   int front, mat, node; /* node: the primitive (for lazy sphere UV) */
+  int prim;             /* the sphere, quad or ConstantMedium whose hit this is (oracle_world_hit_batch) */
   vec3 outward_local;   /* sphere outward normal (for get_sphere_uv) */
 } hitrec;
 
@@ -683,8 +684,16 @@ static int obj_hit(ctx_t* cx, int id, const ray_t* r, real tmin, real tmax, hitr
       }
       return obj_hit(cx, sc->kids[n->first + 1], r, tmin, tmax, rec);
     }
-    case RT_OBJ_SPHERE: return sphere_hit(cx, n, id, r, tmin, tmax, rec);
-    case RT_OBJ_QUAD: return quad_hit(cx, n, r, tmin, tmax, rec);
+    case RT_OBJ_SPHERE: {
+      int h = sphere_hit(cx, n, id, r, tmin, tmax, rec);
+      if (h) rec->prim = id;
+      return h;
+    }
+    case RT_OBJ_QUAD: {
+      int h = quad_hit(cx, n, r, tmin, tmax, rec);
+      if (h) rec->prim = id;
+      return h;
+    }
     case RT_OBJ_TRANSLATE: { /* transform.rs:57-69 */
       CNT(cx, RT_OP_TRANSLATE);
       ray_t lr = {vsub(r->o, n->off), r->d, r->tm};
@@ -705,7 +714,11 @@ static int obj_hit(ctx_t* cx, int id, const ray_t* r, real tmin, real tmax, hitr
       rec->normal = v3(FMA(c, nn.x, s * nn.z), nn.y, FMA(-s, nn.x, c * nn.z));
       return 1;
     }
-    case RT_OBJ_VOLUME: return volume_hit(cx, n, r, tmin, tmax, rec, t_rng);
+    case RT_OBJ_VOLUME: {
+      int h = volume_hit(cx, n, r, tmin, tmax, rec, t_rng);
+      if (h) rec->prim = id;
+      return h;
+    }
   }
   return 0;
 }
@@ -1300,6 +1313,63 @@ EXPORT int oracle_world_hit(const rt_scene_blob* blob, const double* ray7, doubl
   }
   free_scene(&sc);
   return h;
+}
+/* world.hit for n rays (rays7: o3, d3, time) of one blob, parsed once. Each ray's generator is
+ * seeded from its key (keys: seed, pixel, sample as three uint64 per ray) with rng_seed, so a
+ * ConstantMedium's free-flight draw is the draw the device takes for the same key. out, 8 doubles
+ * per ray: hit, t, mat, front, prim, the generator's state afterwards (s0, s1), 0. prim counts
+ * the spheres, quads and ConstantMediums of the world in the blob's (pre-order) sequence: the hit
+ * is the prim-th of them (a ConstantMedium's boundary primitives are counted after it). */
+EXPORT int oracle_world_hit_batch(const rt_scene_blob* blob, const double* rays7, const uint64_t* keys,
+                                  int n, double tmin, double tmax, double* out) {
+  oscene sc;
+  if (parse_scene(blob, &sc)) return -1;
+  ctx_t cx;
+  memset(&cx, 0, sizeof(cx));
+  cx.sc = &sc;
+  int* ordinal = (int*)calloc((size_t)sc.n_nodes + 1, sizeof(int));
+  for (int i = 0, k = 0; i < sc.n_nodes; ++i) {
+    int tag = sc.nodes[i].tag;
+    ordinal[i] = (tag == RT_OBJ_SPHERE || tag == RT_OBJ_QUAD || tag == RT_OBJ_VOLUME) ? k++ : -1;
+  }
+  for (int i = 0; i < n; ++i) {
+    const double* q = rays7 + 7 * (size_t)i;
+    rng_t g;
+    rng_seed(&g, keys[3 * (size_t)i], (uint32_t)keys[3 * (size_t)i + 1], (uint32_t)keys[3 * (size_t)i + 2]);
+    t_rng = &g;
+    ray_t r = {v3(R(q[0]), R(q[1]), R(q[2])), v3(R(q[3]), R(q[4]), R(q[5])), R(q[6])};
+    hitrec rec;
+    memset(&rec, 0, sizeof(rec));
+    int h = obj_hit(&cx, sc.world, &r, R(tmin), R(tmax), &rec);
+    double v[8] = {(double)h, h ? (double)rec.t : 0.0, h ? (double)rec.mat : -1.0,
+                   h ? (double)rec.front : 0.0, h ? (double)ordinal[rec.prim] : -1.0,
+                   (double)g.s[0], (double)g.s[1], 0.0};
+    memcpy(out + 8 * (size_t)i, v, sizeof(v));
+  }
+  t_rng = NULL;
+  free(ordinal);
+  free_scene(&sc);
+  return 0;
+}
+/* Texture::value of texture tex_id at n (u, v, p3) records (uvp: 5 doubles each) -> RGB. */
+EXPORT int oracle_tex_value_batch(const rt_scene_blob* blob, int tex_id, const double* uvp, int n,
+                                  double* out) {
+  oscene sc;
+  if (parse_scene(blob, &sc)) return -1;
+  if (tex_id < 0 || tex_id >= sc.n_texs) {
+    free_scene(&sc);
+    return -2;
+  }
+  ctx_t cx;
+  memset(&cx, 0, sizeof(cx));
+  cx.sc = &sc;
+  for (int i = 0; i < n; ++i) {
+    const double* q = uvp + 5 * (size_t)i;
+    vec3 c = tex_value(&cx, tex_id, R(q[0]), R(q[1]), v3(R(q[2]), R(q[3]), R(q[4])));
+    out[3 * (size_t)i] = c.x, out[3 * (size_t)i + 1] = c.y, out[3 * (size_t)i + 2] = c.z;
+  }
+  free_scene(&sc);
+  return 0;
 }
 /* Light-PDF value and a generated direction at `origin` (pdf.rs:80-100): out = [pdf, dir3]. */
 EXPORT int oracle_light_pdf(const rt_scene_blob* blob, const double* origin3, const double* dir3,

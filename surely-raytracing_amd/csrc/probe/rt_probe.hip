@@ -84,6 +84,7 @@ __device__ __forceinline__ Rng seeded(const double* in) {  // seed_lo, seed_hi, 
 
 // ---------------------------------------------------------------- reciprocals and roots
 PROBE(rcp_nr, 1, 1) { out[0] = rcp_nr(in[0]); }
+PROBE(rcp_nr1, 1, 1) { out[0] = rcp_nr1(in[0]); }
 PROBE(div_nr, 2, 1) { out[0] = div_nr(in[0], in[1]); }
 PROBE(rsq_nr, 1, 1) { out[0] = rsq_nr(in[0]); }
 PROBE(sqrt_nr, 1, 1) { out[0] = sqrt_nr(in[0]); }
@@ -143,12 +144,17 @@ PROBE(sphere_test_v, 13, 5) {
   out[0] = h ? 1.0 : 0.0, out[1] = t, out[2] = a, out[3] = hb, out[4] = disc;
 }
 // in: K, h0, qk, lo0, lo1, hi0, hi1, o3, d3, tmin, tmax, sentinel. out: hit, t_out, t_plane,
-// plane_inr. r = rcp_nr(d) per component, as the walkers pass it.
-PROBE(aquad_test, 16, 4) {
+// plane_inr. Two forms, by the reciprocal handed over per component: aquad_test_nr1 with
+// r = rcp_nr1(d), which is what every caller passes (traverse, volume_two_hits, the BVH walkers,
+// light_leaf_pdf, the generated walkers), and aquad_test with the two-step r = rcp_nr(d).
+namespace {
+template <bool NR1>
+__device__ __forceinline__ void aquad_probe(const double* in, double* out) {
   Ctr<false> C;
   const AQuad q = {(uint32_t)in[1], in[2], in[3], in[4], in[5], in[6]};
   const d3 o = in3(in + 7), d = in3(in + 10);
-  const d3 r = mk(rcp_nr(d.x), rcp_nr(d.y), rcp_nr(d.z));
+  const d3 r = NR1 ? mk(rcp_nr1(d.x), rcp_nr1(d.y), rcp_nr1(d.z))
+                   : mk(rcp_nr(d.x), rcp_nr(d.y), rcp_nr(d.z));
   double t = in[15], tp = 0.0;
   bool inr = false, h;
   const int K = (int)in[0];
@@ -160,6 +166,9 @@ PROBE(aquad_test, 16, 4) {
     h = aquad_test<false, 2>(q, o, d, r, in[13], in[14], t, C, tp, inr);
   out[0] = h ? 1.0 : 0.0, out[1] = t, out[2] = tp, out[3] = inr ? 1.0 : 0.0;
 }
+}  // namespace
+PROBE(aquad_test, 16, 4) { aquad_probe<false>(in, out); }
+PROBE(aquad_test_nr1, 16, 4) { aquad_probe<true>(in, out); }
 // in: two doubles in the place of a record's four header words, the general payload d0-15
 // (rt_layout.h QUAD), o3, d3, tmin, tmax, sentinel, one pad (records stay 16-byte aligned for
 // ld3's paired loads). out: hit, t_out.

@@ -522,7 +522,7 @@ __device__ __forceinline__ bool quad_test(Ptr q, d3 o, d3 d, double tmin, double
 }
 
 // The same test for an axis-aligned quad (rt_layout.h RTL_QUAD_AXIS): bit-identical results,
-// with r = rcp_nr(d) computed once per batch instead of once per quad.
+// with r = rcp_nr1(d) computed once per batch instead of once per quad.
 template <int K>
 struct ic {  // an int as a type (compile-time axis of a generic lambda's argument)
   static constexpr int value = K;
@@ -594,7 +594,7 @@ __device__ __forceinline__ bool aquad_test(const AQuad& q, d3 o, d3 d, d3 r, dou
   return hit;
 }
 // A world QUAD record (batch member or single): branch on its axis code (wave-uniform in UNI
-// traversal); r = rcp_nr(d) of the current frame.
+// traversal); r = rcp_nr1(d) of the current frame.
 template <bool COUNT, class Ptr>
 __device__ __forceinline__ bool world_quad_test(Ptr Q, d3 o, d3 d, d3 r, double tmin, double tmax,
                                                 double& t_out, Ctr<COUNT>& C) {

@@ -48,6 +48,12 @@ def lib(precision: int = 32) -> C.CDLL:
         L.oracle_world_hit.restype = C.c_int
         L.oracle_world_hit.argtypes = [C.POINTER(RtSceneBlob), C.c_void_p, C.c_double,
                                        C.c_double, C.c_void_p]
+        L.oracle_world_hit_batch.restype = C.c_int
+        L.oracle_world_hit_batch.argtypes = [C.POINTER(RtSceneBlob), C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_double, C.c_double, C.c_void_p]
+        L.oracle_tex_value_batch.restype = C.c_int
+        L.oracle_tex_value_batch.argtypes = [C.POINTER(RtSceneBlob), C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p]
         L.oracle_light_pdf.restype = C.c_int
         L.oracle_light_pdf.argtypes = [C.POINTER(RtSceneBlob), C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -148,6 +154,34 @@ def world_hit(blob, ray7, tmin=1e-4, tmax=float("inf"), precision: int = 64):
     if h < 0:
         raise RuntimeError("bad blob")
     return out if h else None
+
+
+def world_hit_batch(blob, rays7, keys=None, tmin=1e-4, tmax=float("inf"), precision: int = 64):
+    """world.hit for n rays (o3, d3, time), the blob parsed once; keys: (seed, pixel, sample) per
+    ray, the stream a ConstantMedium draws from (all zero when None). -> [n, 8] float64: hit, t,
+    mat, front, prim (the hit's place among the world's spheres, quads and ConstantMediums in blob
+    order), the generator's state afterwards (s0, s1), 0."""
+    r = np.ascontiguousarray(rays7, np.float64).reshape(-1, 7)
+    k = np.zeros((r.shape[0], 3), np.uint64) if keys is None else np.ascontiguousarray(
+        keys, np.uint64).reshape(-1, 3)
+    assert k.shape[0] == r.shape[0]
+    out = np.zeros((r.shape[0], 8), np.float64)
+    rc = lib(precision).oracle_world_hit_batch(blob.ref(), r.ctypes.data, k.ctypes.data, r.shape[0],
+                                               tmin, tmax, out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"oracle_world_hit_batch: {rc}")
+    return out
+
+
+def tex_value_batch(blob, tex_id, uvp, precision: int = 64) -> np.ndarray:
+    """Texture::value of one texture at n records (u, v, p3) -> [n, 3] float64."""
+    a = np.ascontiguousarray(uvp, np.float64).reshape(-1, 5)
+    out = np.zeros((a.shape[0], 3), np.float64)
+    rc = lib(precision).oracle_tex_value_batch(blob.ref(), int(tex_id), a.ctypes.data, a.shape[0],
+                                               out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"oracle_tex_value_batch: {rc}")
+    return out
 
 
 def light_pdf(blob, origin, direction, precision: int = 64) -> float:

@@ -30,7 +30,8 @@ Measured on an MI355X (the same table stands in DESIGN.md §2):
   device worst / reference worst (vector-operation rule, bound: a factor 2)
     random_cosine_direction 2.31e-16 / 6.95e-16    random_unit_vector 2.73e-16 / 2.21e-16
     sphere_test_v t         8.53e-13 / 9.96e-13    quad_test t        2.57e-15 / 2.39e-15
-    aquad_test<0,1,2> t     1.72e-16, 2.12e-16, 1.85e-16: the oracle's values exactly
+    aquad_test<0,1,2> t     1.72e-16, 2.12e-16, 1.85e-16: the oracle's values exactly, with
+                            r = rcp_nr(d) and with r = rcp_nr1(d), which is what the callers pass
     rotate_y_in             1.57e-16 / 1.88e-16    rotate_y_out       1.81e-16 / 1.68e-16
     reflect                 3.59e-16 / 4.92e-16    refract            3.94e-16 / 6.04e-16
     refract, critical angle 1.44e-08 / 1.44e-08    unit_vector        3.01e-16 / 2.56e-16
@@ -532,8 +533,15 @@ AXIS_QUADS = {0: ((3, -1, -1), (0, 2, 0), (0, 0, 2)), 1: ((-1, 3, -1), (2, 0, 0)
 GENERAL_QUAD = ((0.5, -1.25, 2.0), (1.5, 0.5, 0.25), (-0.5, 2.0, 1.0))
 
 
-@pytest.mark.parametrize("K", [0, 1, 2])
-def test_aquad_test_exact_cases(gpu_available, K):
+# aquad_test_nr1 forms r with rcp_nr1 (one Newton step), as every caller of aquad_test does;
+# aquad_test with the two-step rcp_nr (whose cases keep the ids [0], [1], [2])
+AQUAD_FORMS = pytest.mark.parametrize("K,form", [
+    pytest.param(K, form, id=f"{K}{tag}") for form, tag in (("aquad_test", ""), ("aquad_test_nr1", "-nr1"))
+    for K in (0, 1, 2)])
+
+
+@AQUAD_FORMS
+def test_aquad_test_exact_cases(gpu_available, K, form):
     blob, k, (consts, gen) = _quad_case(*AXIS_QUADS[K])
     assert k == K
     _, qk, lo0, lo1, hi0, hi1 = consts
@@ -565,7 +573,7 @@ def test_aquad_test_exact_cases(gpu_available, K):
     ]
     # (A NaN planar coordinate, which the accept comparisons let through, needs a non-finite ray:
     # there the reference's n . o or n . d is NaN as well and the test misses. Not a case here.)
-    got = P.run("aquad_test", [_aquad_rec(K, consts, o, d, a, b) for o, d, a, b, _ in cases])
+    got = P.run(form, [_aquad_rec(K, consts, o, d, a, b) for o, d, a, b, _ in cases])
     gq = P.run("quad_test", [_gquad_rec(gen, o, d, a, b) for o, d, a, b, _ in cases])
     for (o, d, a, b, want), g, gg in zip(cases, got, gq):
         ot = _oracle_t(blob, o, d, a, b)
@@ -644,11 +652,11 @@ def _quad_rays(rng, q, u, v, n):
     return out
 
 
-@pytest.mark.parametrize("K", [0, 1, 2])
-def test_aquad_test_random_rays(gpu_available, K):
+@AQUAD_FORMS
+def test_aquad_test_random_rays(gpu_available, K, form):
     blob, k, (consts, _) = _quad_case(*AXIS_QUADS[K])
     rays = _quad_rays(np.random.default_rng(110 + K), *AXIS_QUADS[K], 1024)
-    got = P.run("aquad_test", [_aquad_rec(K, consts, *ray) for ray in rays])
+    got = P.run(form, [_aquad_rec(K, consts, *ray) for ray in rays])
     left_out, hits, dev_w, ora_w = 0, 0, Fr(0), Fr(0)
     for (o, d, tmin, tmax), g in zip(rays, got):
         hit, t, pinr, guard = _aquad_exact(K, consts, o, d, tmin, tmax)
@@ -669,9 +677,9 @@ def test_aquad_test_random_rays(gpu_available, K):
         dev_w = max(dev_w, abs(Fr(float(g[1])) - t) / t)
         ora_w = max(ora_w, abs(Fr(ot) - t) / t)
     share = left_out / len(rays)
-    print(f"aquad_test<{K}>: {len(rays)} rays, {hits} hits, guard band leaves out {100 * share:.2f} %")
+    print(f"{form}<{K}>: {len(rays)} rays, {hits} hits, guard band leaves out {100 * share:.2f} %")
     assert share <= 0.01 and 0.2 * len(rays) < hits < 0.8 * len(rays)
-    _rule(f"aquad_test<{K}> t", float(dev_w), float(ora_w))
+    _rule(f"{form}<{K}> t", float(dev_w), float(ora_w))
 
 
 def test_quad_test_random_rays(gpu_available):

@@ -338,3 +338,105 @@ def test_perlin_turb_matches_the_reference_formulas():
     ref = [_turb_reference(ranvec.tolist(), perms.tolist(), p) for p in pts.tolist()]
     assert np.array_equal(out, np.array(ref))
     assert 0.0 < out.mean() < 2.0
+
+
+# ---------------------------------------------------------------- batch hooks
+def test_world_hit_batch_is_the_one_ray_hook_and_keys_a_volume_draw():
+    """oracle_world_hit_batch parses once and seeds each ray's generator from its key. Without a
+    volume it is oracle_world_hit ray for ray; prim names the primitive in blob order. With a
+    ConstantMedium the free-flight draw is the key's first draw (constant_medium.rs:41-95)."""
+    def build(sc):
+        m = [sc.lambertian((0.1 * k, 0.5, 0.5)) for k in range(4)]
+        return sc.hittable_list(
+            sc.sphere((0, 0, 0), 1.0, m[0]), sc.quad((-1, -1, 3), (2, 0, 0), (0, 2, 0), m[1]),
+            sc.translate(sc.rotate_y(sc.sphere((0, 0, 0), 0.5, m[2]), 30.0), (0, 3, 0)),
+            sc.sphere_moving((4, 0, 0), (4, 1, 0), 0.5, m[3])), None
+    blob = _scene(build)
+    rng = np.random.default_rng(5)
+    o = rng.uniform(-6, 6, (256, 3))
+    tgt = np.array([(0, 0, 0), (0, 0, 3), (0, 3, 0), (4, 0.5, 0)])[rng.integers(0, 4, 256)]
+    d = tgt + rng.uniform(-0.7, 0.7, (256, 3)) - o
+    rays = np.concatenate([o, d, rng.random((256, 1))], 1)
+    got = O.world_hit_batch(blob, rays, None, 1e-4, 50.0)
+    hits = 0
+    for r, g in zip(rays, got):
+        one = O.world_hit(blob, r, 1e-4, 50.0)
+        assert bool(g[0]) == (one is not None)
+        if one is not None:
+            hits += 1
+            assert g[1] == one[0] and g[2] == one[8] and g[3] == one[7]
+            assert g[4] == g[2]  # one material per primitive, in blob order
+        else:
+            assert g[1:5].tolist() == [0.0, -1.0, 0.0, -1.0]
+    assert 60 < hits < 230
+    # known answers: the sphere from outside, the quad behind it through tmax, a miss
+    ka = O.world_hit_batch(blob, [[0, 0, -5, 0, 0, 1, 0], [0, 0, 1.5, 0, 0, 1, 0], [0, 9, -5, 0, 0, 1, 0]])
+    assert ka[:, :5].tolist() == [[1, 4.0, 0, 1, 0], [1, 1.5, 1, 0, 1], [0, 0, -1, 0, -1]]  # the quad from behind (n = +z)
+    # no volume: no draw, the state afterwards is the seeded state
+    keys = np.array([[(5 << 32) | 3, 17 * k + 1, k] for k in range(256)], np.uint64)
+    st = O.world_hit_batch(blob, rays, keys, 1e-4, 50.0)
+    assert np.array_equal(st[:, :5], got[:, :5])
+    for k, s in zip(keys.tolist(), st):
+        first = O.rng_u32(k[0], k[1], k[2], 1)
+        assert first[0] == (int(s[5]) * 0x9E3779BB) & 0xFFFFFFFF  # undrawn: its next output is the first
+
+    def fog(sc):
+        return sc.hittable_list(sc.constant_medium(sc.sphere((0, 0, 0), 1.0, sc.lambertian((1, 1, 1))),
+                                                   0.75, (1, 1, 1))), None
+    vb = _scene(fog)
+    ray = [0.0, 0.0, -5.0, 0.0, 0.0, 2.0, 0.0]  # |d| = 2: t1 = 2, t2 = 3, 2 units inside
+    keys = np.array([[9, k, 2 * k] for k in range(64)], np.uint64)
+    out = O.world_hit_batch(vb, np.tile(ray, (64, 1)), keys)
+    n_hit = 0
+    for k, g in zip(keys.tolist(), out):
+        u = O.rng_draws(k[0], k[1], k[2], 1)[0]
+        dist = (-1.0 / 0.75) * math.log(u)
+        assert bool(g[0]) == (not dist > 2.0)
+        two = O.rng_u32(k[0], k[1], k[2], 2)
+        assert two[1] == (int(g[5]) * 0x9E3779BB) & 0xFFFFFFFF  # exactly one draw was taken
+        if g[0]:
+            n_hit += 1
+            assert g[1] == 2.0 + dist / 2.0 and g[4] == 0
+    assert 30 < n_hit < 64
+
+
+def test_tex_value_batch_known_answers():
+    """oracle_tex_value_batch over Texture::value (texture.rs): solid, checker parity of
+    floor(inv_scale p) (71-81), image lookup with the v flip and clamps (95-107, rt_image.rs:37-46),
+    and noise = 0.5 (1 + sin(s z + 10 turb)) on the same Perlin table as oracle_perlin_turb."""
+    sc = rt.Scene(7)
+    red, blue = sc.solid_color((1, 0, 0)), sc.solid_color((0, 0, 1))
+    chk = sc.checker_texture(0.5, red, blue)
+    img = np.arange(2 * 3 * 3, dtype=np.uint8).reshape(2, 3, 3) * 10  # H = 2, W = 3
+    im = sc.image_texture(img)
+    noi = sc.noise_texture(4.0)
+    mats = [sc.lambertian(tex=t) for t in (red, chk, im, noi)]
+    blob = sc.serialize(sc.hittable_list(*[sc.sphere((3 * k, 0, 0), 1.0, m) for k, m in enumerate(mats)]), None)
+    # the serialiser numbers textures and materials itself: sphere k (a 16-slot record after the
+    # list's 8) carries its material, whose second slot is the texture
+    s = blob.slots
+    w0 = blob.header()["world_off"]
+    red, chk, im, noi = (int(s[int(s[6]) + 8 * int(s[w0 + 8 + 16 * k + 1]) + 1]) for k in range(4))
+    assert O.tex_value_batch(blob, red, [[0.3, 0.4, 1, 2, 3]]).tolist() == [[1, 0, 0]]
+    pts = [[0, 0, 0.25, 0.25, 0.25], [0, 0, 0.75, 0.25, 0.25], [0, 0, -0.25, 0.25, 0.25],
+           [0, 0, 0.5, 0.5, 0.5], [0, 0, 0.5, 0.5, 0.49]]
+    want = [[1, 0, 0], [0, 0, 1], [0, 0, 1], [0, 0, 1], [1, 0, 0]]  # sums 0, 1, -1, 3, 2
+    assert O.tex_value_batch(blob, chk, pts).tolist() == want
+    uv = [[0.0, 0.0], [0.0, 1.0], [0.99, 0.49], [1.0, 1.0], [-3.0, 7.0], [0.5, 0.5]]
+    # (y, x): j = v H, y = H - j - 1 clamped to H - 1; at v = 1 the u32 difference wraps (release
+    # arithmetic) and the clamp gives the bottom row, H - 1
+    rows = [(1, 0), (1, 0), (1, 2), (1, 2), (1, 0), (0, 1)]
+    got = O.tex_value_batch(blob, im, [u + [0, 0, 0] for u in uv])
+    assert np.array_equal(got, np.array([img[y, x] * (1.0 / 255.0) for y, x in rows]))
+    p = np.random.default_rng(3).uniform(-3, 3, (64, 3))
+    got = O.tex_value_batch(blob, noi, np.concatenate([np.zeros((64, 2)), p], 1))
+    base = int(s[8])
+    ranvec = s[base:base + 768].view(np.float64).reshape(256, 3).copy()
+    perms = s[base + 768:base + 1536].astype(np.int32).reshape(3, 256).copy()
+    sp = np.ascontiguousarray(p * 4.0)
+    turb = np.zeros(64)
+    O.lib(64).oracle_perlin_turb(ranvec.ctypes.data, perms.ctypes.data, sp.ctypes.data, 64, turb.ctypes.data)
+    want = np.array([0.5 * (1.0 + math.sin(10.0 * t + z)) for t, z in zip(turb.tolist(), sp[:, 2].tolist())])
+    assert np.array_equal(got, np.stack([want] * 3, 1)) and want.std() > 0.05
+    with pytest.raises(RuntimeError):
+        O.tex_value_batch(blob, blob.header()["n_textures"], [[0, 0, 0, 0, 0]])
