@@ -48,8 +48,8 @@ $(OBJ)/rt_device.o: $(CSRC)/rt_device.hip $(DEV_HDR)
 $(OBJ)/rt_aov.o: $(CSRC)/rt_aov.hip $(CSRC)/rt_aov.h $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-# the a-trous denoisers (rt_denoise.h, rt_denoise_var.h are ahead-of-time only: not in JIT_HDR)
-$(OBJ)/rt_denoise.o: $(CSRC)/rt_denoise.hip $(CSRC)/rt_denoise.h $(CSRC)/rt_denoise_var.h $(DEV_HDR)
+# the a-trous denoisers (rt_denoise.h is ahead-of-time only: not in JIT_HDR)
+$(OBJ)/rt_denoise.o: $(CSRC)/rt_denoise.hip $(CSRC)/rt_denoise.h $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJ)/%.o: $(CSRC)/%.cpp $(DEV_HDR)

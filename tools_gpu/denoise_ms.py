@@ -1,7 +1,8 @@
 """Device time of the a-trous denoiser (rt_denoise_device) next to the beauty render and the AOV
 pass of the same frame: each warmed up, then alternated in one process; the median (and minimum)
 ms_kernel over the rounds. The denoise is also timed at 1 .. LEVELS levels: the increments are the
-cost of each further level, and level 0's figure carries dn_prepare. The traffic floor of a level is
+cost of each further level (one dn_level<0, STEP, FINAL> launch: STEP 1 and 2 from LDS tiles, then
+the direct form), and level 0's figure carries dn_prepare. The traffic floor of a level is
 48 B read + 16 B written per pixel at 8 TB/s; dn_prepare (60 B read, 48 B written) is left out of it.
 With TRUTH_SPP the clipped-[0,1] RMSE of the noisy and of the denoised frame against a TRUTH_SPP
 render at seed 7 is printed too.
