@@ -498,6 +498,104 @@ int  rt_denoise_var(rt_denoiser* dn, const rt_denoise_var_params* p, const float
                     const float* m2, const float* aov, float* out, float* var_out,
                     rt_stats* stats);
 
+/* ---- adaptive sampling: tile-list renders driven by the sample moments --------------------------
+ * The consumer of the moments: render some 8x8 tiles and not others, over stratum rows that cover
+ * the pixel evenly, and stop a tile once the between-row estimate of its error is small.
+ *
+ * rt_render_tiles_device: rt_render_moments_device restricted to a list of tiles and a strided
+ * set of stratum rows. tiles: HOST array of n_list tile indices of the call's tile grid
+ * (tile = ty * ceil(W/8) + tx over the call's n_rows x W pixels), strictly ascending, each <
+ * tiles_x * tiles_y; validated on the host (RT_ERR_INVALID_ARG) before any HIP call and copied
+ * before the call returns. Stratum rows rendered: sj_begin + k * sj_step, k in [0, sj_count);
+ * sj_step >= 1, sj_count >= 1 (0 does not mean "all" here), last row < sqrt_spp. accum/m2: full
+ * n_rows*W*3 device buffers; only pixels of listed tiles are read or written (overwritten or added
+ * to as RT_FLAG_OVERWRITE says, exactly as rt_render_moments_device does per pixel); m2 may be
+ * NULL. With the full list and sj_step 1 both buffers are those of rt_render_moments_device bit for
+ * bit; with sj_step = sqrt_spp and sj_count 1 a tile's pixels are rt_render_device's for that row.
+ * RT_FLAG_INTERPRETER and RT_FLAG_REFERENCE_BVH are honoured; RT_FLAG_COUNT_OPS is
+ * RT_ERR_INVALID_ARG (the op-counting kernels have no tile-list variant); n_rows > 32760 is
+ * RT_ERR_UNSUPPORTED (no split into sub-renders: the tile grid is the call's); n_list == 0 or
+ * n_rows == 0 returns RT_OK and touches nothing. Asynchronous on hip_stream; stats != NULL
+ * synchronises; rt_stats as rt_render_device fills it, samples = pixel-samples of the listed
+ * tiles. Re-entrancy, slots and lifetime are those of rt_render_device. */
+int rt_render_tiles_device(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                           const uint32_t* tiles, uint32_t n_list, int32_t sj_step,
+                           float* accum_rgb_device, float* m2_rgb_device, void* hip_stream,
+                           rt_stats* stats);
+
+/* Host only. Pass p of P over sqrt_spp rows renders rows p, p+P, p+2P, ...: every pass covers the
+ * pixel's stratum rows evenly (a contiguous prefix of rows would sample only the top of the
+ * pixel). Valid for 1 <= passes <= sqrt_spp / 2 and 0 <= pass < passes, so pass 0 always holds at
+ * least 2 rows and the variance estimate exists; otherwise RT_ERR_INVALID_ARG. */
+int rt_adaptive_schedule(int sqrt_spp, int passes, int pass, int* sj_begin, int* sj_step,
+                         int* sj_count);
+
+/* A handle owns a device workspace (12 B per tile), a mutex that serialises its calls and an
+ * ordering event, as rt_denoiser does. Null pointers and value ranges are checked before the
+ * handle is read and before any HIP call. width x height is a full contiguous frame whose 8x8
+ * tile grid is that of a render of height rows; rows_held: HOST array, one uint32 per tile, the
+ * stratum rows the tile's sums hold (<= sqrt_spp).
+ *
+ * rt_adaptive_tile_error (synchronous): per pixel of a tile with n = rows_held[tile] >= 2 and
+ * B = n * sqrt_spp, evaluated in f64 from the f32 inputs,
+ *   var_c = max(0, Q_c - S_c^2 / n) * n / ((n - 1) * B^2)      (the estimator above)
+ *   e = sqrt(var_r + var_g + var_b) / (max(S_r,0)/B + max(S_g,0)/B + max(S_b,0)/B + floor),
+ * the relative standard error of the pixel mean; floor (finite, > 0) keeps black pixels finite.
+ * A pixel with a non-finite S, Q or e is invalid: it contributes nothing and is counted in
+ * *n_invalid_out (may be NULL); more samples do not cure a NaN. err_out[tile] (HOST, one float per
+ * tile) = the maximum of e over the tile's valid pixels rounded to f32, 0 if it has none; +inf for
+ * a tile with rows_held < 2, whose pixels are not examined. height == 0 returns RT_OK.
+ *
+ * rt_adaptive_resolve_device (asynchronous on hip_stream; rows_held is copied before it returns;
+ * every rows_held >= 1): per pixel with B_p = rows_held[tile] * sqrt_spp,
+ *   out = (float)((double)accum * (sqrt_spp^2 / B_p)),  samples = B_p  (one float per pixel,
+ * samples_dev may be NULL): the sums in the scale of a full-spp render, which write_color and
+ * rt_denoise with beauty_samples = spp take unchanged. A pixel that holds every row is a bitwise
+ * copy. out_dev may equal accum_dev. */
+typedef struct rt_adaptive rt_adaptive;
+int  rt_adaptive_create(int device, rt_adaptive** out);
+void rt_adaptive_destroy(rt_adaptive* ad);
+int  rt_adaptive_tile_error(rt_adaptive* ad, int width, int height, int sqrt_spp, double floor,
+                            const float* accum_dev, const float* m2_dev, const uint32_t* rows_held,
+                            float* err_out, uint64_t* n_invalid_out, void* hip_stream);
+int  rt_adaptive_resolve_device(rt_adaptive* ad, int width, int height, int sqrt_spp,
+                                const uint32_t* rows_held, const float* accum_dev, float* out_dev,
+                                float* samples_dev, void* hip_stream);
+
+/* The driver (synchronous: accum, m2 and the optional outputs are complete on return).
+ * opts->sj_begin and sj_count must be 0, RT_FLAG_OVERWRITE must be set (the moments must be the
+ * frame's own) and RT_FLAG_COUNT_OPS clear; row_begin, row_step, n_rows (<= 32760), seed and the
+ * other flags as for rt_render_device. With S = sqrt_spp and P = passes:
+ *   1. the active set starts as all tiles;
+ *   2. pass p renders the active list (rt_render_tiles_device) over rt_adaptive_schedule(S, P, p);
+ *      pass 0 overwrites, later passes add;
+ *   3. rows_held[t] += sj_count for active t;
+ *   4. if p + 1 >= min_passes and p + 1 < P: rt_adaptive_tile_error, and the next active set is
+ *      {t active : err_t > threshold}, kept ascending;
+ *   5. stop when the active set is empty or p = P - 1;
+ *   6. a tile never re-enters the active set.
+ * out_dev (may be NULL) and samples_dev (may be NULL) receive rt_adaptive_resolve_device's outputs;
+ * rows_held_out (HOST, one per tile, may be NULL); tiles_per_pass (HOST, P entries, may be NULL):
+ * the length of each pass's list, 0 for passes not run. rt_stats: samples = pixel-samples actually
+ * traced, launches = path-kernel launches, ms_kernel = the passes' kernel times summed, ms_total =
+ * wall time. Not covered: rt_multi_* and the RCCL path, adaptive AOVs. */
+typedef struct rt_adaptive_params {  /* 24 bytes, no padding */
+  int32_t passes;      /* P, 1..sqrt_spp/2 */
+  int32_t min_passes;  /* 1..P: passes every tile receives */
+  double threshold;    /* a tile continues while its error > threshold; may be negative or +inf; NaN invalid */
+  double floor;        /* rt_adaptive_tile_error's floor: finite, > 0 */
+} rt_adaptive_params;
+int rt_render_adaptive_device(rt_adaptive* ad, rt_scene* scene, const rt_camera* cam,
+                              const rt_render_opts* opts, const rt_adaptive_params* params,
+                              float* accum_rgb_device, float* m2_rgb_device, float* out_dev,
+                              float* samples_dev, uint32_t* rows_held_out, uint32_t* tiles_per_pass,
+                              void* hip_stream, rt_stats* stats);
+/* the same with HOST buffers (accum, m2: n_rows*W*3 floats, written; out and samples may be NULL) */
+int rt_render_adaptive(rt_adaptive* ad, rt_scene* scene, const rt_camera* cam,
+                       const rt_render_opts* opts, const rt_adaptive_params* params,
+                       float* accum_rgb, float* m2_rgb, float* out, float* samples,
+                       uint32_t* rows_held_out, uint32_t* tiles_per_pass, rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,7 +163,17 @@ pub struct rt_denoise_var_params {
     pub sigma_albedo: f32,
 }
 
-/// Opaque handles (rt_scene, rt_multi, rt_denoiser).
+/// Parameters of the adaptive driver (rt_render_adaptive_device); 24 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_adaptive_params {
+    pub passes: i32,     // P, 1..sqrt_spp/2
+    pub min_passes: i32, // 1..P: passes every tile receives
+    pub threshold: f64,  // a tile continues while its error > threshold; NaN invalid
+    pub floor: f64,      // finite, > 0
+}
+
+/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive).
 #[repr(C)]
 pub struct rt_scene {
     _private: [u8; 0],
@@ -174,6 +184,10 @@ pub struct rt_multi {
 }
 #[repr(C)]
 pub struct rt_denoiser {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct rt_adaptive {
     _private: [u8; 0],
 }
 
@@ -247,4 +261,34 @@ extern "C" {
     pub fn rt_denoise_var(dn: *mut rt_denoiser, p: *const rt_denoise_var_params,
                           beauty: *const f32, m2: *const f32, aov: *const f32, out: *mut f32,
                           var_out: *mut f32, stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_tiles_device(scene: *mut rt_scene, cam: *const rt_camera,
+                                  opts: *const rt_render_opts, tiles: *const u32, n_list: u32,
+                                  sj_step: i32, accum_rgb_device: *mut f32,
+                                  m2_rgb_device: *mut f32, hip_stream: *mut c_void,
+                                  stats: *mut rt_stats) -> c_int;
+    pub fn rt_adaptive_schedule(sqrt_spp: c_int, passes: c_int, pass: c_int,
+                                sj_begin: *mut c_int, sj_step: *mut c_int,
+                                sj_count: *mut c_int) -> c_int;
+    pub fn rt_adaptive_create(device: c_int, out: *mut *mut rt_adaptive) -> c_int;
+    pub fn rt_adaptive_destroy(ad: *mut rt_adaptive);
+    pub fn rt_adaptive_tile_error(ad: *mut rt_adaptive, width: c_int, height: c_int,
+                                  sqrt_spp: c_int, floor: f64, accum_dev: *const f32,
+                                  m2_dev: *const f32, rows_held: *const u32, err_out: *mut f32,
+                                  n_invalid_out: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn rt_adaptive_resolve_device(ad: *mut rt_adaptive, width: c_int, height: c_int,
+                                      sqrt_spp: c_int, rows_held: *const u32,
+                                      accum_dev: *const f32, out_dev: *mut f32,
+                                      samples_dev: *mut f32, hip_stream: *mut c_void) -> c_int;
+    pub fn rt_render_adaptive_device(ad: *mut rt_adaptive, scene: *mut rt_scene,
+                                     cam: *const rt_camera, opts: *const rt_render_opts,
+                                     params: *const rt_adaptive_params,
+                                     accum_rgb_device: *mut f32, m2_rgb_device: *mut f32,
+                                     out_dev: *mut f32, samples_dev: *mut f32,
+                                     rows_held_out: *mut u32, tiles_per_pass: *mut u32,
+                                     hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_adaptive(ad: *mut rt_adaptive, scene: *mut rt_scene, cam: *const rt_camera,
+                              opts: *const rt_render_opts, params: *const rt_adaptive_params,
+                              accum_rgb: *mut f32, m2_rgb: *mut f32, out: *mut f32,
+                              samples: *mut f32, rows_held_out: *mut u32,
+                              tiles_per_pass: *mut u32, stats: *mut rt_stats) -> c_int;
 }

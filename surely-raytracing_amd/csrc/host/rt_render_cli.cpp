@@ -5,12 +5,16 @@
 //   -> with --denoise: rt_render_aov + rt_denoise (the a-trous filter over the first-hit guides)
 //   -> with --denoise-var: rt_render_moments + rt_render_aov + rt_denoise_var (the same filter
 //      guided by the per-pixel variance of the row totals; needs spp >= 4)
+//   -> with --adaptive T: rt_render_adaptive (tiles stop once their estimated relative error is
+//      <= T) and the resolved frame; combines with --denoise (the filter reads the resolved frame)
 //   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
-//                      [--denoise-var [levels]] [--out file.ppm]
+//                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
+//                      [--out file.ppm]
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +49,9 @@ int main(int argc, char** argv) {
   bool refsem = false, autoexp = false;
   int denoise_levels = 0;  // 0 = no denoising
   bool denoise_var = false;  // the variance-guided filter instead of the plain one
+  bool adaptive = false;
+  double ad_threshold = 0.0, ad_floor = 1e-2;
+  int ad_passes = 0;  // 0 = min(8, sqrt_spp / 2)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -83,11 +90,23 @@ int main(int argc, char** argv) {
       denoise_levels = -1;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
         denoise_levels = std::atoi(argv[++i]);
-    } else if (a == "--out") out = next();
+    } else if (a == "--adaptive") {
+      adaptive = true;
+      ad_threshold = std::atof(next());
+    } else if (a == "--passes") ad_passes = std::atoi(next());
+    else if (a == "--floor") ad_floor = std::atof(next());
+    else if (a == "--out") out = next();
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
     }
+  }
+  if (adaptive && denoise_levels && denoise_var) {
+    std::fprintf(stderr,
+                 "--adaptive does not combine with --denoise-var: that filter takes one beauty_rows "
+                 "for the whole frame, and an adaptive frame holds a different number of stratum "
+                 "rows per tile (use --denoise, which reads the resolved frame)\n");
+    return 2;
   }
   rth_scene* s = rth_scene_new(build_seed);
   int32_t world = -1, lights = -1;
@@ -116,7 +135,51 @@ int main(int argc, char** argv) {
   std::vector<float> accum((size_t)cam.image_width * cam.image_height * 3, 0.f);
   rt_stats st;
   int rc;
-  if (!denoise_levels) {
+  if (adaptive) {
+    // the adaptive driver; with --denoise the plain filter over its resolved frame
+    rt_scene* sc = nullptr;
+    rt_adaptive* ad = nullptr;
+    rt_denoiser* dn = nullptr;
+    rt_adaptive_params ap;
+    ap.passes = ad_passes > 0 ? ad_passes : std::max(1, std::min(8, cam.sqrt_spp / 2));
+    ap.min_passes = 1;
+    ap.threshold = ad_threshold;
+    ap.floor = ad_floor;
+    std::vector<float> sums(accum.size(), 0.f), m2(accum.size(), 0.f);
+    std::vector<uint32_t> per((size_t)ap.passes, 0u);
+    rc = rt_scene_create(&blob, device, &sc);
+    if (rc == RT_OK) rc = rt_adaptive_create(device, &ad);
+    if (rc == RT_OK)
+      rc = rt_render_adaptive(ad, sc, &cam, &o, &ap, sums.data(), m2.data(), accum.data(), nullptr,
+                              nullptr, per.data(), &st);
+    if (rc == RT_OK) {
+      const uint64_t total = (uint64_t)cam.image_width * cam.image_height * cam.samples_per_pixel;
+      std::fprintf(stderr, "adaptive: traced %llu of %llu samples (%.1f %%), tiles per pass:",
+                   (unsigned long long)st.samples, (unsigned long long)total,
+                   100.0 * (double)st.samples / (double)total);
+      for (uint32_t t : per) std::fprintf(stderr, " %u", t);
+      std::fprintf(stderr, "\n");
+    }
+    if (rc == RT_OK && denoise_levels) {
+      rt_denoise_params dp;
+      std::vector<float> aov((size_t)cam.image_width * cam.image_height * RT_AOV_CHANNELS, 0.f);
+      rt_stats st_aov, st_dn;
+      rc = rt_denoise_default_params(cam.image_width, cam.image_height, cam.samples_per_pixel,
+                                     cam.samples_per_pixel, &dp);
+      if (rc == RT_OK && denoise_levels > 0) dp.levels = denoise_levels;
+      if (rc == RT_OK) rc = rt_render_aov(sc, &cam, &o, aov.data(), &st_aov);
+      if (rc == RT_OK) rc = rt_denoiser_create(device, &dn);
+      if (rc == RT_OK) rc = rt_denoise(dn, &dp, accum.data(), aov.data(), accum.data(), &st_dn);
+      if (rc == RT_OK)
+        std::fprintf(stderr, "aov %.2f ms, denoise (%d levels) %.3f ms\n", st_aov.ms_kernel,
+                     dp.levels, st_dn.ms_kernel);
+    }
+    if (rc != RT_OK) std::fprintf(stderr, "rt_render --adaptive: %d %s\n", rc, rt_last_error());
+    rt_denoiser_destroy(dn);
+    rt_adaptive_destroy(ad);
+    rt_scene_destroy(sc);
+    if (rc != RT_OK) return 1;
+  } else if (!denoise_levels) {
     rc = rt_render_blob(&blob, &cam, &o, accum.data(), &st);
     if (rc != RT_OK) {
       std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error());

@@ -43,6 +43,15 @@
 using namespace rtk;
 using namespace rts;
 
+namespace rts {
+// The tile-list variant (trace_body's TILES) of the ahead-of-time product kernel that
+// render_device_rows chose (rt_tiles.hip: a translation unit of its own, so the build compiles its
+// 18 instances beside this file's). set 0: [vol][tex][bvh]; 1: staged [vol][tex]; 2: BVH without
+// the walker's volume branch [no two-walk interpreter][tex]; 3: nested volumes [bvh].
+typedef void (*tile_kern_t)(TraceParams);
+RTS_HIDDEN tile_kern_t tile_trace_kernel(int set, int idx);
+}  // namespace rts
+
 namespace {
 
 // Ahead-of-time kernels: the interpreter traversal, one per feature combination.
@@ -76,35 +85,48 @@ struct MomentsOut<true> {
   double* tot2;  // the chunks' carry of q
   float* m2;     // the caller's second buffer
 };
-template <bool M2>
+// TILES (rt_render_tiles_device): one wave per entry of the launch's tile list; n_tiles is the
+// list's length, the pixel position comes from the listed tile, and the pairs (q0 = entry * n_sj)
+// and the chunks' carries (64 pixels per entry) stay compact, indexed by the position in the list.
+// The plain instantiation (TileIn<false>, an empty argument) names none of it.
+template <bool TILES>
+struct TileIn {};
+template <>
+struct TileIn<true> {
+  const uint32_t* list;
+};
+template <bool M2, bool TILES = false>
 __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part,
                                                  double* __restrict__ tot,
                                                  float* __restrict__ accum, int W, int n_rows,
                                                  int tiles_x, int n_tiles, int n_sj, int S,
                                                  int n_pairs_r, int n_pairs_a, int mode,
-                                                 MomentsOut<M2> mo) {
+                                                 MomentsOut<M2> mo, TileIn<TILES> ti = {}) {
   const int tile_id = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   const int pv = threadIdx.x & 63;
   if (tile_id >= n_tiles) return;
-  const int tx = tile_id % tiles_x, ty = tile_id / tiles_x;
+  int tile_px = tile_id;  // the tile of the call's grid whose pixels this wave sums
+  if constexpr (TILES) tile_px = (int)ti.list[tile_id];
+  const int tx = tile_px % tiles_x, ty = tile_px / tiles_x;
   const int tile_w = min(kWaveTile, W - tx * kWaveTile);
   const int tile_h = min(kWaveTile, n_rows - ty * kWaveTile);
   if (pv >= tile_w * tile_h) return;
   const int x = tx * kWaveTile + pv % tile_w, kr = ty * kWaveTile + pv / tile_w;
   const size_t i = (size_t)kr * W + x;
+  const size_t ic = TILES ? (size_t)tile_id * 64 + pv : i;  // the pixel's carry between chunks
   const int n_blk = (S + kPoolSi - 1) / kPoolSi;
   double t0 = 0.0, t1 = 0.0, t2 = 0.0;
   if (!(mode & 1)) {
-    t0 = tot[3 * i];
-    t1 = tot[3 * i + 1];
-    t2 = tot[3 * i + 2];
+    t0 = tot[3 * ic];
+    t1 = tot[3 * ic + 1];
+    t2 = tot[3 * ic + 2];
   }
   double m0 = 0.0, m1 = 0.0, m2c = 0.0;  // M2: sum of R^2
   if constexpr (M2) {
     if (!(mode & 1)) {
-      m0 = mo.tot2[3 * i];
-      m1 = mo.tot2[3 * i + 1];
-      m2c = mo.tot2[3 * i + 2];
+      m0 = mo.tot2[3 * ic];
+      m1 = mo.tot2[3 * ic + 1];
+      m2c = mo.tot2[3 * ic + 2];
     }
   }
   const int q0 = tile_id * n_sj;  // this tile's pairs q0 .. q0 + n_sj - 1 (s_j order)
@@ -200,7 +222,7 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
       a[2] = (float)((double)a[2] + t2);
     }
   } else {
-    tot[3 * i] = t0, tot[3 * i + 1] = t1, tot[3 * i + 2] = t2;
+    tot[3 * ic] = t0, tot[3 * ic + 1] = t1, tot[3 * ic + 2] = t2;
   }
   if constexpr (M2) {
     float* b = mo.m2 + 3 * i;
@@ -212,7 +234,7 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
         b[2] = (float)((double)b[2] + m2c);
       }
     } else {
-      mo.tot2[3 * i] = m0, mo.tot2[3 * i + 1] = m1, mo.tot2[3 * i + 2] = m2c;
+      mo.tot2[3 * ic] = m0, mo.tot2[3 * ic + 1] = m1, mo.tot2[3 * ic + 2] = m2c;
     }
   }
 }
@@ -513,6 +535,7 @@ void rt_scene_destroy(rt_scene* sc) {
   for (const auto& sl : sc->slots) {
     if (sl->work) (void)hipFree(sl->work);
     if (sl->work2) (void)hipFree(sl->work2);
+    if (sl->tiles) (void)hipFree(sl->tiles);
     if (sl->ops) (void)hipFree(sl->ops);
     if (sl->done) (void)hipEventDestroy(sl->done);
     if (sl->ev0) (void)hipEventDestroy(sl->ev0);
@@ -545,6 +568,18 @@ int rt_jit_check(const rt_scene_blob* blob, const char* arch, int* state, char* 
     if (rc != 0) {
       *state = -2;
       out = log;
+    }
+    // RT_JIT_CHECK_TILES=1 (tools/jit_cache_fill.py): the tile-list variant of the same kernel
+    // too, so that the code-object cache holds both; the returned source is the plain walker's
+    const char* tv = std::getenv("RT_JIT_CHECK_TILES");
+    if (rc == 0 && tv && std::strcmp(tv, "1") == 0) {
+      rtj::Flags tf = rtj::product_flags(F, true);
+      tf.tiles = true;
+      rc = rtj::compile(rtj::kernel_source(walker, tf), arch, &code, &log);
+      if (rc != 0) {
+        *state = -2;
+        out = log;
+      }
     }
   }
   if (msg && msg_len) {
@@ -625,10 +660,23 @@ int rts::acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStrea
   }
 }
 
+// A tile-list render's list (rt_render_tiles_device), validated by the entry point: strictly
+// ascending indices of the call's tile grid. n_px: the pixels of the listed tiles.
+struct TileJob {
+  const uint32_t* tiles;
+  uint32_t n_list;
+  int sj_step;
+  uint64_t n_px;
+};
+
 // m2 != nullptr: a moments render (rt_render_moments_device), which also writes the second
-// moments of the row totals; every other step is the plain render's.
+// moments of the row totals; every other step is the plain render's. tj != nullptr: a tile-list
+// render (rt_render_tiles_device): the launch's pairs run over the list's entries and the strided
+// stratum rows sj_begin + k * sj_step, through the TILES variants of the same kernels; LDS plan,
+// kernel choice, slot, chunking and stats are shared.
 static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
-                              float* accum, float* m2, void* stream_v, rt_stats* stats) {
+                              float* accum, float* m2, const TileJob* tj, void* stream_v,
+                              rt_stats* stats) {
   auto t0 = std::chrono::steady_clock::now();
   if (!sc || !cam || !opts || !accum) return set_err(RT_ERR_INVALID_ARG, "null argument");
   const int W = cam->image_width, S = cam->sqrt_spp;
@@ -648,7 +696,9 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   if (S > 32768) return set_err(RT_ERR_UNSUPPORTED, "spp > 2^30 (sqrt_spp > 32768)");
   const int sj0 = opts->sj_count > 0 ? opts->sj_begin : 0;
   const int n_sj = opts->sj_count > 0 ? opts->sj_count : S;
-  if (sj0 < 0 || sj0 + n_sj > S) return set_err(RT_ERR_INVALID_ARG, "bad stratum range");
+  const int sj_step = tj ? tj->sj_step : 1;
+  if (sj0 < 0 || (int64_t)sj0 + (int64_t)(n_sj - 1) * sj_step + 1 > S)
+    return set_err(RT_ERR_INVALID_ARG, "bad stratum range");
   if (sc->hdr.n_lights == 0 && (opts->flags & RT_FLAG_SEMANTICS_REFERENCE) && sc->hdr.pdf_materials)
     return set_err(RT_ERR_EMPTY_LIGHTS,
                    "empty light list with a diffuse/volume material: the reference panics "
@@ -742,7 +792,9 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   P.seed_hi = (uint32_t)(opts->seed >> 32);
   P.tiles_x = (W + kWaveTile - 1) / kWaveTile;
   const int tiles_y = (opts->n_rows + kWaveTile - 1) / kWaveTile;
-  const int n_tiles = P.tiles_x * tiles_y;
+  // the launch's tiles: the call's whole grid, or the entries of the list
+  const int n_tiles = tj ? (int)tj->n_list : P.tiles_x * tiles_y;
+  P.sj_step = sj_step;
   P.n_blk = (S + kPoolSi - 1) / kPoolSi;
   typedef void (*kern_t)(TraceParams);
   // [count][vol][tex][bvh]; a scene without a BVH whose tables are staged in LDS runs the
@@ -781,6 +833,9 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   const int vb = (novoli ? 4 : 0) + (kidx >= 8 ? 2 : 0) + (tex ? 1 : 0);
   kern_t kern = staged ? table_staged[kidx / 2 - 8] : (novolb ? table_bvh_novolb[vb] : table[kidx]);
   int kslot = novolb ? 32 + vb : kidx;
+  // the same choice among the tile-list variants (rt_tiles.hip; product kernels only)
+  int tset = staged ? 1 : (novolb ? 2 : 0);
+  int tidx = staged ? kidx / 2 - 8 : (novolb ? (novoli ? 2 : 0) + (tex ? 1 : 0) : kidx);
   // ConstantMedium nested in volume boundaries (rt_flatten.cpp: at most RTL_VOLUME_NEST deep):
   // the generic texture/volume kernels that walk them (no scene-specialised kernel)
   static const kern_t table_nested[4] = {
@@ -792,10 +847,16 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     const int ni = ((opts->flags & RT_FLAG_COUNT_OPS) ? 2 : 0) + (bvh ? 1 : 0);
     kern = table_nested[ni];
     kslot = 44 + ni;
+    tset = 3;
+    tidx = bvh ? 1 : 0;
+  }
+  if (tj) {
+    kern = tile_trace_kernel(tset, tidx);
+    if (!kern) return set_err(RT_ERR_INVALID_ARG, "no tile-list variant of this kernel");
   }
   hipFunction_t jfn = nullptr;
   if (want_jit && lds_bytes + static_lds <= sc->lds_module_max) {
-    rtj::Kernel& jk = sc->jit_k[(tex ? 1 : 0) + (staged ? 2 : 0)];
+    rtj::Kernel& jk = sc->jit_k[(tex ? 1 : 0) + (staged ? 2 : 0) + (tj ? 4 : 0)];
     if (!jk.fn) {
       std::string log;
       rtj::Flags jf;
@@ -805,6 +866,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
       jf.staged = staged;
       jf.volb = novolb ? false : vol;
       jf.voli = !novoli;
+      jf.tiles = tj != nullptr;
       if (rtj::get_kernel(sc->jit_walker, sc->device, jf, &jk, &log) != 0) {
         sc->jit_state = -2;
         sc->jit_msg = log;
@@ -838,6 +900,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
       kslot = 40 + (tex ? 1 : 0) + (staged ? 2 : 0);
     }
   }
+  if (tj) kslot += rt_scene::kKernelSlots / 2;  // the tile-list variants' occupancy entries
   // (module kernels take their dynamic LDS size at launch)
   if (!jfn && lds_bytes > (64u << 10))
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -889,7 +952,9 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     sp.values = sp.r + (sp.a - sp.r) * P.n_blk + tb * S;  // 64-value slots
     return sp;
   };
-  const size_t tot_bytes = (n_px * 3 * sizeof(double) + 255) & ~(size_t)255;
+  // the chunks' carries: one f64 RGB value per pixel of the call, or per pixel slot of the list
+  const size_t n_carry = tj ? (size_t)n_tiles * 64 : n_px;
+  const size_t tot_bytes = (n_carry * 3 * sizeof(double) + 255) & ~(size_t)255;
   const size_t val_bytes = (size_t)64 * 3 * sizeof(double);  // one f64 RGB value per pixel
   auto part_bytes = [&](int cn) { return (size_t)split(cn).values * val_bytes; };
   // a launch's f64 RGB outputs are indexed in 32 bits (end_sample) and its pools in 31
@@ -927,24 +992,47 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     HIP_TRY(hipMalloc(&sl->work2, tot_bytes));
     sl->work2_bytes = tot_bytes;
   }
+  if (tj) {
+    // the list travels through the slot: a host copy (the caller may free its list on return) and
+    // a device buffer, both touched only after the slot's previous render has finished (its
+    // kernels read the device buffer, its upload the host copy)
+    if (sl->recorded && (sl->tiles_busy || tj->n_list > sl->tiles_cap))
+      HIP_TRY(hipEventSynchronize(sl->done));
+    sl->tiles_busy = false;
+    if (tj->n_list > sl->tiles_cap) {
+      if (sl->tiles) HIP_TRY(hipFree(sl->tiles));
+      sl->tiles = nullptr;
+      sl->tiles_cap = 0;
+      HIP_TRY(hipMalloc(&sl->tiles, (size_t)tj->n_list * sizeof(uint32_t)));
+      sl->tiles_cap = tj->n_list;
+    }
+    sl->tiles_host.assign(tj->tiles, tj->tiles + tj->n_list);
+    P.tile_list = sl->tiles;
+  }
   double* tot = (double*)sl->work;
   double* tot2 = (double*)sl->work2;  // read and written only between chunks
   P.part = (double*)(sl->work + tot_bytes);
   hold.stream = stream;
   hold.enqueued = true;  // from here on a failure still records `done` (SlotHold)
   if (ops_buf) HIP_TRY(hipMemsetAsync(sl->ops, 0, sizeof(unsigned long long) * 32, stream));
+  if (tj) {
+    sl->tiles_busy = true;
+    HIP_TRY(hipMemcpyAsync(sl->tiles, sl->tiles_host.data(), (size_t)tj->n_list * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, stream));
+  }
 #ifdef RT_PROF
   HIP_TRY(hipMemsetAsync(sl->ops + 40, 0, sizeof(unsigned long long) * 21, stream));
 #endif
   if (stats) HIP_TRY(hipEventRecord(sl->ev0, stream));
   uint64_t out_bytes = 0;
   uint32_t launches = 0;
-  for (int c0 = sj0; c0 < sj0 + n_sj; c0 += chunk) {
-    const int cn = std::min(chunk, sj0 + n_sj - c0);
+  // chunk k0 renders the call's stratum rows sj0 + (k0 .. k0 + cn - 1) * sj_step
+  for (int k0 = 0; k0 < n_sj; k0 += chunk) {
+    const int cn = std::min(chunk, n_sj - k0);
     out_bytes += part_bytes(cn);
     ++launches;
     const Split sp = split(cn);
-    P.sj0 = c0;
+    P.sj0 = sj0 + k0 * sj_step;
     P.n_sj = cn;
     P.n_pairs_r = (int)sp.r;
     P.n_pairs_a = (int)sp.a;
@@ -965,17 +1053,25 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     HIP_TRY(hipEventRecord(sc->tev[ring][1], stream));
     sc->tev_render[ring] = sc->n_render;
     ++sc->n_tev;
-    const int mode = (c0 == sj0 ? 1 : 0) | (c0 + cn == sj0 + n_sj ? 2 : 0) |
+    const int mode = (k0 == 0 ? 1 : 0) | (k0 + cn == n_sj ? 2 : 0) |
                      ((opts->flags & RT_FLAG_OVERWRITE) ? 4 : 0);
     const dim3 rgrid((unsigned)((n_tiles + 3) / 4));
-    if (m2)
+    if (tj && m2)
+      hipLaunchKernelGGL((rt_reduce<true, true>), rgrid, dim3(256), 0, stream, P.part, tot, accum,
+                         W, opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
+                         MomentsOut<true>{tot2, m2}, TileIn<true>{sl->tiles});
+    else if (tj)
+      hipLaunchKernelGGL((rt_reduce<false, true>), rgrid, dim3(256), 0, stream, P.part, tot, accum,
+                         W, opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
+                         MomentsOut<false>{}, TileIn<true>{sl->tiles});
+    else if (m2)
       hipLaunchKernelGGL(rt_reduce<true>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
                          opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<true>{tot2, m2});
+                         MomentsOut<true>{tot2, m2}, TileIn<false>{});
     else
       hipLaunchKernelGGL(rt_reduce<false>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
                          opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<false>{});
+                         MomentsOut<false>{}, TileIn<false>{});
     HIP_TRY(hipGetLastError());
   }
   ++sc->n_render;
@@ -990,7 +1086,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, sl->ev0, sl->ev1));
     stats->ms_kernel = ms;
-    stats->samples = (uint64_t)n_px * (uint64_t)n_sj * (uint64_t)S;
+    stats->samples = (uint64_t)(tj ? tj->n_px : n_px) * (uint64_t)n_sj * (uint64_t)S;
     stats->out_bytes = out_bytes;
     stats->launches = launches;
     if (ops_buf) {
@@ -1008,7 +1104,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
 static int render_device_split(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
                                float* accum, float* m2, void* stream_v, rt_stats* stats) {
   if (opts->n_rows <= kRowsPerCall || cam->image_width <= 0)
-    return render_device_rows(sc, cam, opts, accum, m2, stream_v, stats);
+    return render_device_rows(sc, cam, opts, accum, m2, nullptr, stream_v, stats);
   auto t0 = std::chrono::steady_clock::now();
   rt_stats part{}, sum{};
   for (int k0 = 0; k0 < opts->n_rows; k0 += kRowsPerCall) {
@@ -1016,8 +1112,8 @@ static int render_device_split(rt_scene* sc, const rt_camera* cam, const rt_rend
     o.row_begin = opts->row_begin + k0 * opts->row_step;
     o.n_rows = std::min(kRowsPerCall, opts->n_rows - k0);
     const size_t off = (size_t)k0 * cam->image_width * 3;
-    const int rc = render_device_rows(sc, cam, &o, accum + off, m2 ? m2 + off : nullptr, stream_v,
-                                      stats ? &part : nullptr);
+    const int rc = render_device_rows(sc, cam, &o, accum + off, m2 ? m2 + off : nullptr, nullptr,
+                                      stream_v, stats ? &part : nullptr);
     if (rc != RT_OK) return rc;
     if (stats) {
       sum.ms_kernel += part.ms_kernel;
@@ -1047,6 +1143,38 @@ int rt_render_moments_device(rt_scene* sc, const rt_camera* cam, const rt_render
                              float* accum, float* m2, void* stream_v, rt_stats* stats) {
   if (!sc || !cam || !opts || !accum || !m2) return set_err(RT_ERR_INVALID_ARG, "null argument");
   return render_device_split(sc, cam, opts, accum, m2, stream_v, stats);
+}
+
+int rt_render_tiles_device(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
+                           const uint32_t* tiles, uint32_t n_list, int32_t sj_step, float* accum,
+                           float* m2, void* stream_v, rt_stats* stats) {
+  if (!sc || !cam || !opts || !accum || (!tiles && n_list))
+    return set_err(RT_ERR_INVALID_ARG, "null argument");
+  if (opts->flags & RT_FLAG_COUNT_OPS)
+    return set_err(RT_ERR_INVALID_ARG, "RT_FLAG_COUNT_OPS: no tile-list variant of the counting kernels");
+  if (cam->image_width <= 0 || opts->n_rows < 0) return set_err(RT_ERR_INVALID_ARG, "bad size");
+  if (sj_step < 1 || opts->sj_count < 1 || opts->sj_begin < 0)
+    return set_err(RT_ERR_INVALID_ARG, "tile render: sj_step >= 1, sj_count >= 1, sj_begin >= 0");
+  if (opts->n_rows > kRowsPerCall)
+    return set_err(RT_ERR_UNSUPPORTED, "tile render: n_rows > 32760 in one call");
+  // the device never sees an unvalidated tile index: strictly ascending, inside the call's grid
+  const int64_t W = cam->image_width, H = opts->n_rows;
+  const int64_t tiles_x = (W + kWaveTile - 1) / kWaveTile, tiles_y = (H + kWaveTile - 1) / kWaveTile;
+  uint64_t n_px = 0;
+  for (uint32_t k = 0; k < n_list; ++k) {
+    const int64_t t = tiles[k];
+    if (t >= tiles_x * tiles_y || (k && tiles[k] <= tiles[k - 1]))
+      return set_err(RT_ERR_INVALID_ARG, "tile list: entries must be strictly ascending and inside the grid");
+    const int64_t tx = t % tiles_x, ty = t / tiles_x;
+    n_px += (uint64_t)(std::min<int64_t>(kWaveTile, W - tx * kWaveTile) *
+                       std::min<int64_t>(kWaveTile, H - ty * kWaveTile));
+  }
+  if (n_list == 0 || opts->n_rows == 0) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return RT_OK;
+  }
+  const TileJob tj{tiles, n_list, (int)sj_step, n_px};
+  return render_device_rows(sc, cam, opts, accum, m2, &tj, stream_v, stats);
 }
 
 // Profiling builds (-DRT_PROF, not shipped): the ordered-BVH walk counters of the last render

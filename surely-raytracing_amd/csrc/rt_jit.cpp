@@ -713,7 +713,10 @@ std::string kernel_source(const std::string& walker, const Flags& f) {
          "(MinWaves<" << b(f.vol) << ", " << b(f.tex) << ", " << b(f.bvh)
       << ", true>::value)) void rt_trace_jit(TraceParams P) {\n"
       << "  trace_body<false, " << b(f.vol) << ", " << b(f.tex) << ", " << b(f.bvh) << ", "
-      << b(f.staged) << ", " << b(f.volb) << ", " << b(f.voli) << ", TravGen>(P);\n}\n";
+      << b(f.staged) << ", " << b(f.volb) << ", " << b(f.voli) << ", TravGen"
+      // the plain kernel's text stays as it was: the flag is part of the source (and so of the
+      // module cache's and the code-object cache's keys) only when set
+      << (f.tiles ? ", true" : "") << ">(P);\n}\n";
   return src.str();
 }
 

@@ -21,6 +21,7 @@ std::string generate(const rtf::FlatScene& F, std::string* why);
 // the same as the ahead-of-time interpreter kernel the scene would otherwise launch.
 struct Flags {
   bool vol = false, tex = false, staged = false, bvh = false, volb = false, voli = true;
+  bool tiles = false;  // the tile-list variant (trace_body's TILES; rt_render_tiles_device)
 };
 // Flags of the product kernel for scene header `hdr` (rt_device.hip's kernel choice).
 Flags product_flags(const rtf::FlatScene& F, bool staged);

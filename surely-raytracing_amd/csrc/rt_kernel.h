@@ -395,6 +395,11 @@ struct TraceParams {
   int W, n_rows, row_begin, row_step, sqrt_spp, sj0, n_sj, max_depth;
   uint32_t seed_lo, seed_hi;
   int tiles_x;
+  // tile-list launches (trace_body<..., TILES = true>, rt_render_tiles_device): pair q belongs to
+  // list entry q / n_sj, whose pixels are those of tile tile_list[q / n_sj] of the call's tile
+  // grid, and renders stratum row sj0 + (q % n_sj) * sj_step. Plain launches read neither.
+  const uint32_t* __restrict__ tile_list;
+  int sj_step;
 };
 
 // The kernel's only argument sits at offset 0 of the kernarg segment. Camera constants are read
@@ -2100,7 +2105,11 @@ typedef TravInterpN<0> TravInterp;
 
 // The path kernel body; instantiated by rt_device.hip (interpreter) and by scene-specialised
 // JIT kernels. Its __global__ wrapper passes TraceParams as the only kernel argument (kparams()).
-template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, class Trav>
+// TILES: the launch's pairs are compact over a host-validated list of tiles and a strided set of
+// stratum rows (TraceParams::tile_list, sj_step); only the pixel coordinates and the stratum row of
+// the RNG key and jitter come from them, every pair, slot and pool index stays the position in the list.
+template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, class Trav,
+          bool TILES = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   // STAGED: the small-table prefix is in LDS (P.stage_scene) and per-lane table reads are
   // ds_reads through 32-bit LDS pointers; otherwise they read the global tables.
@@ -2312,14 +2321,19 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         tailp = q >= Q->n_pairs_a;
         obase = tailp ? (uint32_t)(r + (Q->n_pairs_a - r) * nb + (q - Q->n_pairs_a) * Q->sqrt_spp) * 64u
                       : id * 64u;
-        const int tile = q / Q->n_sj;
+        const int ent = q / Q->n_sj;  // the pair's tile: its index, or its position in the list
+        int tile = ent;
+        if constexpr (TILES) tile = (int)Q->tile_list[ent];
         tx = tile % Q->tiles_x;
         ty = tile / Q->tiles_x;
         tile_w = imin(kWaveTile, Q->W - tx * kWaveTile);
         nv = tile_w * imin(kWaveTile, Q->n_rows - ty * kWaveTile);
         si0 = blk * kPoolSi;
         pool = tailp ? nv * imin(kPoolSi, Q->sqrt_spp - si0) : nv;
-        s_jp = Q->sj0 + (q - tile * Q->n_sj);
+        if constexpr (TILES)
+          s_jp = Q->sj0 + (q - ent * Q->n_sj) * Q->sj_step;
+        else
+          s_jp = Q->sj0 + (q - ent * Q->n_sj);
       } else {
         more = false;
         pool = 0;

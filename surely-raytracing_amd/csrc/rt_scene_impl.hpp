@@ -61,6 +61,12 @@ struct RenderSlot {
   size_t work_bytes = 0;
   uint8_t* work2 = nullptr;  // moments renders in several chunks: the f64 running sums of R^2
   size_t work2_bytes = 0;
+  // tile-list renders: the list on the device and the host copy it is uploaded from; both are
+  // rewritten, freed or regrown only after `done` (tiles_busy: the last render here used them)
+  uint32_t* tiles = nullptr;
+  size_t tiles_cap = 0;  // entries
+  std::vector<uint32_t> tiles_host;
+  bool tiles_busy = false;
   unsigned long long* ops = nullptr;  // 32 op counters, the pool-queue word (32), profiling (40..)
   unsigned int* queue = nullptr;
   hipEvent_t done = nullptr;  // recorded after the render's last kernel
@@ -87,8 +93,11 @@ struct rt_scene {
   int n_cu = 0;                 // compute units of the device
   size_t mem_total = (size_t)8 << 30;  // device memory (hipMemGetInfo at creation)
   size_t lds_module_max = 64u << 10;  // LDS a module (hiprtc) launch may take (device limit)
-  int resident_blocks[48] = {}; // per kernel variant: blocks resident per CU (0 = not queried)
-  size_t resident_lds[48] = {};  // ... at this dynamic LDS size
+  // per kernel variant: blocks resident per CU (0 = not queried); the second half of the entries
+  // are the tile-list variants of the first
+  static constexpr int kKernelSlots = 96;
+  int resident_blocks[kKernelSlots] = {};
+  size_t resident_lds[kKernelSlots] = {};  // ... at this dynamic LDS size
   int aov_resident[8] = {};      // the same per rt_aov variant (rt_aov.hip)
   size_t aov_resident_lds[8] = {};
   // scene-specialised product kernel (rt_jit.cpp): the generated world walker, compiled on the
@@ -96,7 +105,7 @@ struct rt_scene {
   // generated (jit_msg says why), -2 = compile failed (jit_msg = log; the interpreter runs)
   std::string jit_walker, jit_msg;
   int jit_state = -1;
-  rtj::Kernel jit_k[4];  // [tex][staged]
+  rtj::Kernel jit_k[8];  // [tex][staged][tile-list variant]
   // rt_trace launch timing: one event pair per launch, ring of kTraceRing, tagged by render id
   static constexpr int kTraceRing = 4 * RT_TRACE_HISTORY;
   hipEvent_t tev[kTraceRing][2] = {};

@@ -108,6 +108,11 @@ class RtDenoiseVarParams(C.Structure):
                 ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class RtAdaptiveParams(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("min_passes", C.c_int32), ("threshold", C.c_double),
+                ("floor", C.c_double)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rt error {code}: {msg}")
@@ -233,6 +238,27 @@ def load_device_lib(path: Path) -> C.CDLL:
                                             C.c_void_p, C.POINTER(RtStats)]),
         "rt_denoise_var": (C.c_int, [p, C.POINTER(RtDenoiseVarParams), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_tiles_device": (C.c_int, [p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
+                                             C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_adaptive_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "rt_adaptive_create": (C.c_int, [C.c_int, C.POINTER(p)]),
+        "rt_adaptive_destroy": (None, [p]),
+        "rt_adaptive_tile_error": (C.c_int, [p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.c_void_p]),
+        "rt_adaptive_resolve_device": (C.c_int, [p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_render_adaptive_device": (C.c_int, [p, p, C.POINTER(RtCamera),
+                                                C.POINTER(RtRenderOpts),
+                                                C.POINTER(RtAdaptiveParams), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_adaptive": (C.c_int, [p, p, C.POINTER(RtCamera), C.POINTER(RtRenderOpts),
+                                         C.POINTER(RtAdaptiveParams), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -549,6 +575,22 @@ class DeviceScene:
             C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
 
+    def render_tiles_device(self, cam: RtCamera, opts: RtRenderOpts, tiles, sj_step: int,
+                            accum_ptr: int, m2_ptr: int = 0, stream: int = 0,
+                            stats: bool = False):
+        """Asynchronous rt_render_tiles_device: the 8x8 tiles listed in `tiles` (strictly
+        ascending indices of the call's tile grid, ty * ceil(W / 8) + tx) over the stratum rows
+        opts.sj_begin + k * sj_step, k < opts.sj_count (>= 1), into device buffers of
+        n_rows * W * 3 floats of which only the listed tiles' pixels are touched (m2_ptr 0 = no
+        second moments)."""
+        t = np.ascontiguousarray(tiles, np.uint32)
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_render_tiles_device(
+            self._h, C.byref(cam), C.byref(opts), t.ctypes.data, t.size, sj_step,
+            C.c_void_p(accum_ptr), C.c_void_p(m2_ptr or None), C.c_void_p(stream or None),
+            C.byref(st) if st is not None else None))
+        return st
+
     def render_aov(self, cam: RtCamera, opts: RtRenderOpts, aov: np.ndarray | None = None):
         """Synchronous first-hit AOV pass (rt_render_aov) into a host float32
         (n_rows, W, AOV_CHANNELS) array: per-pixel sums over the call's samples of hits, t (the
@@ -701,6 +743,105 @@ class Denoiser:
             C.c_void_p(aov_ptr), C.c_void_p(out_ptr), C.c_void_p(var_out_ptr or None),
             C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
+
+
+# ---------------------------------------------------------------------------- adaptive sampling
+def adaptive_schedule(sqrt_spp: int, passes: int, pass_: int) -> tuple[int, int, int]:
+    """rt_adaptive_schedule (host only): (sj_begin, sj_step, sj_count) of pass `pass_` of `passes`
+    over sqrt_spp stratum rows: rows pass_, pass_ + passes, ... Valid for 1 <= passes <=
+    sqrt_spp // 2."""
+    b, s, n = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check_dev(device_lib().rt_adaptive_schedule(sqrt_spp, passes, pass_, C.byref(b), C.byref(s),
+                                                 C.byref(n)))
+    return b.value, s.value, n.value
+
+
+def tile_grid(width: int, height: int) -> tuple[int, int]:
+    """(tiles_x, tiles_y) of the 8x8 tile grid of a width x height call."""
+    return (width + 7) // 8, (height + 7) // 8
+
+
+class Adaptive:
+    """Adaptive sampling on one GPU (rt_adaptive_create): per-tile error estimates from the sample
+    moments, the resolve of unevenly sampled sums and the driver that renders only the tiles that
+    have not converged. Calls on one Adaptive are serialised."""
+
+    def __init__(self, device: int = 0):
+        self._lib = device_lib()
+        self.device = device
+        h = C.c_void_p()
+        _check_dev(self._lib.rt_adaptive_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rt_adaptive_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def tile_error(self, width: int, height: int, sqrt_spp: int, floor: float, accum_ptr: int,
+                   m2_ptr: int, rows_held, stream: int = 0):
+        """Synchronous rt_adaptive_tile_error over device sums: returns (err, n_invalid), err a
+        float32 array of one value per tile (the largest relative standard error of its valid
+        pixels; +inf where rows_held < 2)."""
+        rows = np.ascontiguousarray(rows_held, np.uint32)
+        tx, ty = tile_grid(width, height)
+        assert rows.size == tx * ty
+        err = np.zeros(tx * ty, np.float32)
+        inv = C.c_uint64(0)
+        _check_dev(self._lib.rt_adaptive_tile_error(
+            self._h, width, height, sqrt_spp, floor, C.c_void_p(accum_ptr), C.c_void_p(m2_ptr),
+            rows.ctypes.data, err.ctypes.data, C.byref(inv), C.c_void_p(stream or None)))
+        return err, int(inv.value)
+
+    def resolve_device(self, width: int, height: int, sqrt_spp: int, rows_held, accum_ptr: int,
+                       out_ptr: int, samples_ptr: int = 0, stream: int = 0):
+        """Asynchronous rt_adaptive_resolve_device: out = accum * sqrt_spp**2 / samples held, in
+        the scale of a full-spp render (out_ptr may equal accum_ptr); samples_ptr (0 = none)
+        receives the samples each pixel holds."""
+        rows = np.ascontiguousarray(rows_held, np.uint32)
+        tx, ty = tile_grid(width, height)
+        assert rows.size == tx * ty
+        _check_dev(self._lib.rt_adaptive_resolve_device(
+            self._h, width, height, sqrt_spp, rows.ctypes.data, C.c_void_p(accum_ptr),
+            C.c_void_p(out_ptr), C.c_void_p(samples_ptr or None), C.c_void_p(stream or None)))
+
+    def render_device(self, scene: "DeviceScene", cam: RtCamera, opts: RtRenderOpts,
+                      params: RtAdaptiveParams, accum_ptr: int, m2_ptr: int, out_ptr: int = 0,
+                      samples_ptr: int = 0, stream: int = 0):
+        """Synchronous rt_render_adaptive_device over device buffers. Returns (rows_held,
+        tiles_per_pass, stats): the stratum rows each tile ended with, the number of tiles each
+        pass rendered, and RtStats (samples = pixel-samples actually traced)."""
+        tx, ty = tile_grid(cam.image_width, opts.n_rows)
+        rows = np.zeros(tx * ty, np.uint32)
+        per = np.zeros(max(1, params.passes), np.uint32)
+        st = RtStats()
+        _check_dev(self._lib.rt_render_adaptive_device(
+            self._h, scene._h, C.byref(cam), C.byref(opts), C.byref(params),
+            C.c_void_p(accum_ptr), C.c_void_p(m2_ptr), C.c_void_p(out_ptr or None),
+            C.c_void_p(samples_ptr or None), rows.ctypes.data, per.ctypes.data,
+            C.c_void_p(stream or None), C.byref(st)))
+        return rows, per, st
+
+    def render(self, scene: "DeviceScene", cam: RtCamera, opts: RtRenderOpts,
+               params: RtAdaptiveParams):
+        """The driver with host results: returns (out, samples, rows_held, tiles_per_pass, stats),
+        out the resolved (n_rows, W, 3) float32 frame in the scale of a full-spp render
+        (write_color(out, spp)), samples the (n_rows, W) samples each pixel holds."""
+        shape = (opts.n_rows, cam.image_width)
+        acc, m2, out = (np.zeros(shape + (3,), np.float32) for _ in range(3))
+        smp = np.zeros(shape, np.float32)
+        tx, ty = tile_grid(cam.image_width, opts.n_rows)
+        rows = np.zeros(tx * ty, np.uint32)
+        per = np.zeros(max(1, params.passes), np.uint32)
+        st = RtStats()
+        _check_dev(self._lib.rt_render_adaptive(
+            self._h, scene._h, C.byref(cam), C.byref(opts), C.byref(params), acc.ctypes.data,
+            m2.ctypes.data, out.ctypes.data, smp.ctypes.data, rows.ctypes.data, per.ctypes.data,
+            C.byref(st)))
+        return out, smp, rows, per, st
 
 
 def render_par_lights(blob: Blob, cam: RtCamera, seed: int = 1, device: int = 0,
