@@ -226,3 +226,23 @@ __device__ __forceinline__ void P_perlin_turb::apply(const double* in, double* o
                                                      const uint8_t* aux) {
   out[0] = (double)perlin_turb(aux, in3(in));
 }
+
+// ---------------------------------------------------------------- f32 weight constants
+// in: a double. out: the bits of to_w3's component for it, as an integer. The flattener stores the
+// host's (float) cast of a weight constant (rt_layout.h RTL_MATF_SOLID_W) in place of this
+// conversion; tests/test_weight_mirror_gpu.py holds the two together. (Written out, not through
+// PROBE: tests/probe_lib.py lists the probes that take and return plain values.)
+namespace {
+struct P_to_w3_bits {
+  static constexpr int IN = 1, OUT = 1;
+  static __device__ __forceinline__ void apply(const double* in, double* out, const uint8_t*) {
+    const w3 w = to_w3(mk(in[0], in[0], in[0]));
+    out[0] = (double)__builtin_bit_cast(uint32_t, (float)w.x);
+  }
+};
+}  // namespace
+extern "C" __attribute__((visibility("default"))) int rtp_to_w3_bits(const double* in, double* out,
+                                                                     int n) {
+  if (n > 4096) return (int)hipErrorInvalidValue;
+  return probe_run<P_to_w3_bits>(in, out, n, nullptr, 0);
+}

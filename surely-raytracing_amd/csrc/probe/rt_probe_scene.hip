@@ -379,3 +379,24 @@ RTP_API int rtp_scene_records(const rt_scene_blob* blob, double* out, int cap) {
   }
   return (int)S.recs.size();
 }
+
+// The flattened material and texture tables of a scene (any scene: nothing is launched), for the
+// host test of the f32 weight mirrors (tests/test_weight_mirror.py). Copies at most *_cap words
+// each; returns the flattener's status, the table sizes in words through n_mats / n_texs.
+RTP_API int rtp_flat_tables(const rt_scene_blob* blob, uint32_t* mats, int mats_cap, uint32_t* texs,
+                            int texs_cap, int* n_mats, int* n_texs) {
+  if (!blob || !n_mats || !n_texs || mats_cap < 0 || texs_cap < 0 || (mats_cap > 0 && !mats) ||
+      (texs_cap > 0 && !texs))
+    return RTP_ERR_ARG;
+  rtf::FlatScene F;
+  std::string err;
+  const int rc = rtf::flatten(blob, &F, &err);
+  if (rc != RT_OK) return rc;
+  *n_mats = (int)F.mats.size();
+  *n_texs = (int)F.texs.size();
+  const size_t nm = F.mats.size() < (size_t)mats_cap ? F.mats.size() : (size_t)mats_cap;
+  const size_t nt = F.texs.size() < (size_t)texs_cap ? F.texs.size() : (size_t)texs_cap;
+  if (nm) std::memcpy(mats, F.mats.data(), nm * 4);
+  if (nt) std::memcpy(texs, F.texs.data(), nt * 4);
+  return 0;
+}

@@ -108,6 +108,7 @@ int aov_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* op
     P.ddu[k] = cam->defocus_disk_u[k];
     P.ddv[k] = cam->defocus_disk_v[k];
     P.bg[k] = cam->background[k];
+    P.bg_w[k] = (float)cam->background[k];  // the f32 weight the path kernel multiplies by
   }
   P.rs = cam->recip_sqrt_spp;
   P.defocus = cam->defocus_angle > 0.0;

@@ -779,6 +779,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
     P.ddu[k] = cam->defocus_disk_u[k];
     P.ddv[k] = cam->defocus_disk_v[k];
     P.bg[k] = cam->background[k];
+    P.bg_w[k] = (float)cam->background[k];  // the f32 weight the path kernel multiplies by
   }
   P.rs = cam->recip_sqrt_spp;
   P.defocus = cam->defocus_angle > 0.0;

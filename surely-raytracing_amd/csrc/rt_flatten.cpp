@@ -615,6 +615,17 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
     std::memcpy(&d, &s[i], 8);
     return d;
   };
+  // f32 mirror of a weight constant (rt_layout.h RTL_MATF_SOLID_W): the host cast rounds to nearest
+  // even and keeps denormals, as the device's conversion does
+  auto f32_bits = [](double d) {
+    const float f = (float)d;
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+  };
+  auto set_w = [&](uint32_t* o, double x, double y, double z) {
+    o[2] = f32_bits(x), o[3] = f32_bits(y), o[RTL_MAT_WZ] = f32_bits(z);
+  };
   // textures
   F.texs.assign(n_tex * RTL_TEX_WORDS, 0u);
   for (uint64_t t = 0; t < n_tex; ++t) {
@@ -625,6 +636,7 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
     switch (kind) {
       case RT_TEX_SOLID:
         setd(o, 0, rd_f(b + 1)), setd(o, 1, rd_f(b + 2)), setd(o, 2, rd_f(b + 3));
+        o[1] = f32_bits(rd_f(b + 1)), o[2] = f32_bits(rd_f(b + 2)), o[3] = f32_bits(rd_f(b + 3));
         break;
       case RT_TEX_CHECKER: {
         int64_t e = (int64_t)s[b + 2], d = (int64_t)s[b + 3];
@@ -691,18 +703,26 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
         o[0] = (uint32_t)kind | (tex_needs_uv(F.texs, (uint32_t)t, 0) ? RTL_MATF_NEEDS_UV : 0u);
         if (kind != RT_MAT_DIFFUSE_LIGHT) pdf_mats = true;
         if (kind == RT_MAT_ISOTROPIC) isotropic = true;
-        if (F.texs[(size_t)t * RTL_TEX_WORDS] != RT_TEX_SOLID) textured = true;
+        if (F.texs[(size_t)t * RTL_TEX_WORDS] != RT_TEX_SOLID) {
+          textured = true;
+        } else {  // the colour itself, in the record shading has already loaded
+          o[0] |= RTL_MATF_SOLID_W;
+          set_w(o, rd_f(tex_off + t * RT_TEX_SLOTS + 1), rd_f(tex_off + t * RT_TEX_SLOTS + 2),
+                rd_f(tex_off + t * RT_TEX_SLOTS + 3));
+        }
         break;
       }
       case RT_MAT_METAL:  // albedo3 fuzz
         o[0] = (uint32_t)kind;
         setd(o, 0, rd_f(b + 1)), setd(o, 1, rd_f(b + 2)), setd(o, 2, rd_f(b + 3));
         setd(o, 3, rd_f(b + 4));
+        set_w(o, rd_f(b + 1), rd_f(b + 2), rd_f(b + 3));
         break;
       case RT_MAT_DIELECTRIC:  // ir tint3
         o[0] = (uint32_t)kind;
         setd(o, 3, rd_f(b + 1));
         setd(o, 0, rd_f(b + 2)), setd(o, 1, rd_f(b + 3)), setd(o, 2, rd_f(b + 4));
+        set_w(o, rd_f(b + 2), rd_f(b + 3), rd_f(b + 4));
         {
           const double ir = rd_f(b + 1), inv = 1.0 / ir;
           const double rf = (1.0 - inv) / (1.0 + inv), rb = (1.0 - ir) / (1.0 + ir);

@@ -207,6 +207,8 @@ typedef d3 w3;
 __device__ __forceinline__ w3 mkw(wt x, wt y, wt z) { return mk(x, y, z); }
 __device__ __forceinline__ w3 to_w3(d3 v) { return v; }
 __device__ __forceinline__ d3 to_d3(w3 v) { return v; }
+constexpr bool kWMirror = false;  // f64 weights read the f64 fields
+__device__ __forceinline__ w3 bits_w3(uint32_t, uint32_t, uint32_t) { return mk(0., 0., 0.); }
 __device__ __forceinline__ wt rcp_wt(wt b) { return rcp_w(b); }
 __device__ __forceinline__ wt rsq_wt(wt x) { return rsq_nr(x); }
 #else
@@ -219,11 +221,31 @@ __device__ __forceinline__ w3 operator*(w3 a, w3 b) { return {a.x * b.x, a.y * b
 __device__ __forceinline__ w3 operator*(w3 a, wt t) { return {a.x * t, a.y * t, a.z * t}; }
 __device__ __forceinline__ w3 to_w3(d3 v) { return {(float)v.x, (float)v.y, (float)v.z}; }
 __device__ __forceinline__ d3 to_d3(w3 v) { return {(double)v.x, (double)v.y, (double)v.z}; }
+// Weight constants that are fixed when the scene is created (a material's colour, a solid
+// texture's, the background) are stored as f64 for the f64 consumers and again as the bits of their
+// (float) casts (rt_layout.h RTL_MATF_SOLID_W, TraceParams::bg_w): a bounce reads the three words
+// instead of converting three doubles. The host cast and to_w3 give the same bits.
+constexpr bool kWMirror = true;
+__device__ __forceinline__ w3 bits_w3(uint32_t x, uint32_t y, uint32_t z) {
+  return {__builtin_bit_cast(float, x), __builtin_bit_cast(float, y), __builtin_bit_cast(float, z)};
+}
 // 1/b within an ulp; 1/+-0 = +-inf, 1/inf = 0 and NaN stay, as the reference's weights
 __device__ __forceinline__ wt rcp_wt(wt b) { return __builtin_amdgcn_rcpf(b); }
 __device__ __forceinline__ wt rsq_wt(wt x) { return __builtin_amdgcn_rsqf(x); }
 #endif
 constexpr wt kInvPiW = (wt)(1.0 / 3.14159265358979323846);
+// a 32-bit word kept in a weight-typed LDS slot and back: as its bits in an f32 slot, as its value
+// (exact) in an f64 one
+template <class W>
+__device__ __forceinline__ W word_to_slot(uint32_t u) {
+  if constexpr (sizeof(W) == 4) return __builtin_bit_cast(W, u);
+  else return (W)u;
+}
+template <class W>
+__device__ __forceinline__ uint32_t slot_to_word(W w) {
+  if constexpr (sizeof(W) == 4) return __builtin_bit_cast(uint32_t, w);
+  else return (uint32_t)w;
+}
 
 // x^5 correctly rounded, for Schlick's (1 - cos)^5 (material.rs:162 calls powf(5.), i.e. the
 // platform pow). x^2 is formed exactly as a double-double (a + ae), squared and multiplied by x
@@ -390,6 +412,7 @@ struct TraceParams {
   uint32_t row_lds_off;
   uint32_t o_mats, o_texs, o_lights, o_loffs, o_perl;
   double center[3], p00[3], du[3], dv[3], ddu[3], ddv[3], bg[3];
+  float bg_w[3];  // (float)bg: the background as the path kernel's f32 weight
   double rs;
   int defocus;
   int W, n_rows, row_begin, row_step, sqrt_spp, sj0, n_sj, max_depth;
@@ -474,6 +497,25 @@ __device__ __forceinline__ void ld64(Ptr p, uint4& a, uint4& b, uint4& c, uint4&
   e = ld4u(p + 12);
 }
 __device__ __forceinline__ d3 arr3(const double* a) { return mk(a[0], a[1], a[2]); }
+// Record i of a table of `words`-word records, and entry i of a word table. A table staged in LDS
+// is indexed in 32 bits (its pointer is 32 bits wide; a size_t product costs a v_mad_u64_u32 pair
+// where one v_mul_lo_u32 does); global and constant tables keep size_t.
+template <class Ptr>
+struct TabIndex {
+  typedef size_t type;
+};
+template <>
+struct TabIndex<lptr> {
+  typedef uint32_t type;
+};
+template <class Ptr>
+__device__ __forceinline__ Ptr rec_at(Ptr base, uint32_t i, uint32_t words) {
+  return base + (typename TabIndex<Ptr>::type)i * (typename TabIndex<Ptr>::type)words;
+}
+template <class Ptr>
+__device__ __forceinline__ uint32_t word_at(Ptr base, uint32_t i) {
+  return base[(typename TabIndex<Ptr>::type)i];
+}
 
 // ---------------------------------------------------------------- op counters (COUNT build)
 template <bool COUNT>
@@ -1816,9 +1858,9 @@ __device__ __noinline__ float perlin_turb_global(const uint8_t* __restrict__ T, 
 template <bool COUNT, bool TEX, class TT>
 __device__ d3 tex_value(const TraceParams& P, const TT& T, uint32_t id, double u, double v,
                         d3 p, Ctr<COUNT>& C) {
-  if (!TEX) return ld3(T.texs + (size_t)id * RTL_TEX_WORDS, 0);
+  if (!TEX) return ld3(rec_at(T.texs, id, RTL_TEX_WORDS), 0);
   for (int guard = 0; guard < 65; ++guard) {
-    const auto t = T.texs + (size_t)id * RTL_TEX_WORDS;
+    const auto t = rec_at(T.texs, id, RTL_TEX_WORDS);
     uint4 h = ld4u(t);
     if (h.x == RT_TEX_SOLID) return ld3(t, 0);
     if (h.x == RT_TEX_CHECKER) {  // texture.rs:71-81
@@ -2537,7 +2579,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     if (!hit_w) {
       C.inc(RT_OP_MISSES);  // background render.rs:298-309
-      set_le(beta * to_w3(karr3(kparams()->bg)));
+      if constexpr (kWMirror) {
+        const auto bw = kparams()->bg_w;
+        set_le(beta * mkw(bw[0], bw[1], bw[2]));
+      } else {
+        set_le(beta * to_w3(karr3(kparams()->bg)));
+      }
       term = emit_end = true;
       break;
     }
@@ -2561,9 +2608,18 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     d3 normal;
     bool front = true;
     double u = 0., v = 0.;
-    const TP M = T.mats + (size_t)X[2] * RTL_MAT_WORDS;
+    const TP M = rec_at(T.mats, X[2], RTL_MAT_WORDS);
     uint4 mh = ld4u(M);
     const bool needs_uv = TEX && (mh.x & RTL_MATF_NEEDS_UV) != 0u;
+    // the f32 colour this bounce weights by, from the record's mirror words (rt_layout.h): METAL /
+    // DIELECTRIC c, or the SOLID texture's colour of the other kinds (always, without textures)
+    const bool solid_w = kWMirror && (!TEX || (mh.x & RTL_MATF_SOLID_W) != 0u);
+    auto mat_w = [&]() { return bits_w3(mh.z, mh.w, M[RTL_MAT_WZ]); };
+    auto tex_w = [&]() {
+      if constexpr (!kWMirror) return to_w3(tex_value<COUNT, TEX>(P, T, mh.y, u, v, p, C));
+      else if constexpr (!TEX) return mat_w();
+      else return solid_w ? mat_w() : to_w3(tex_value<COUNT, TEX>(P, T, mh.y, u, v, p, C));
+    };
     // the primitive's outward normal per type, then ONE set_face_normal (hittable.rs:22-37) for
     // every lane; a ConstantMedium hit has normal (1, 0, 0) and front_face true
     // (constant_medium.rs:82-90)
@@ -2598,7 +2654,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     PROF(3);
     if ((SC & kScLight) && kind == RT_MAT_DIFFUSE_LIGHT) {  // material.rs:210-222
       C.inc(RT_OP_EMISSIVE_HITS);
-      set_le(front ? beta * to_w3(tex_value<COUNT, TEX>(P, T, mh.y, u, v, p, C)) : mkw(0, 0, 0));
+      set_le(front ? beta * tex_w() : mkw(0, 0, 0));
       term = emit_end = true;
       break;
     }
@@ -2608,7 +2664,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       d3 ruv = random_unit_vector(g);
       p_next = p;
       d_next = vfma(ldd(M, 3), ruv, unit_vector(reflected));
-      set_f(to_w3(ld3(M, 0)));
+      set_f(kWMirror ? mat_w() : to_w3(ld3(M, 0)));
       break;
     }
     // Dielectric (material.rs:166-191), Lambertian and Isotropic (the mixture-PDF branch,
@@ -2628,7 +2684,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     // sphere light at p (object.rs:196, 205-207), shared by Sphere::random and pdf_value
     double sq_in = fma(-cos_t, cos_t, 1.0);
     if ((SC & kScLSphere) && P.sphere_light0 >= 0) {
-      const TP S0 = T.lights + T.loffs[P.sphere_light0];
+      const TP S0 = T.lights + word_at(T.loffs, (uint32_t)P.sphere_light0);
       const d3 cmo = ld3(S0, 0) - p;
       const double r0 = ldd(S0, 3);
       const double arg = 1.0 - div_nr(r0 * r0, dot(cmo, cmo));
@@ -2666,7 +2722,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     w3 factor;
     double cos_sl = cos_sl0;
     if (!diel) {
-      const w3 atten = to_w3(tex_value<COUNT, TEX>(P, T, mh.y, u, v, p, C));
+      const w3 atten = tex_w();
       // Draw order as the reference: mixture coin (above), then light index
       // (hittable.rs:126-129) or nothing, then the two uniforms of whichever generator runs.
       uint32_t ltype = 0, li = 0;
@@ -2674,11 +2730,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if (light_branch) {
         C.inc(RT_OP_LIGHT_GEN);
         li = P.lights_is_list ? rnd_index(g, P.n_lights) : 0u;
-        L = T.lights + T.loffs[li];
+        L = T.lights + word_at(T.loffs, li);
         ltype = L[0] & 0xffu;
         while ((SC & kScLList) && ltype == RTL_LLIST) {  // a nested HittableList: random_int pick (hittable.rs:126-129)
           li = L[1] + rnd_index(g, L[0] >> 8);
-          L = T.lights + T.loffs[li];
+          L = T.lights + word_at(T.loffs, li);
           ltype = L[0] & 0xffu;
         }
       } else {
@@ -2703,6 +2759,16 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         // and CosinePDF::generate (pdf.rs:75-77, vec3.rs:240-250) share one straight-line block:
         // one ONB, one sincos, selects instead of divergent branches.
         const double r1 = rnd(g), r2 = rnd(g);
+        // The generator's state is not read again in this arm, where register pressure peaks (the
+        // ONB, the sincos and both sqrt): it waits in the lane's s_pdf / mat_pdf slots, which are
+        // free from the world query to the end of this arm, instead of in two scratch dwords.
+        // (volatile: the two words must leave the register file, not be forwarded to the loads)
+        constexpr bool PARK = LDSF;
+        typedef volatile __attribute__((address_space(3))) wt* park_t;
+        if constexpr (PARK) {
+          *(park_t)&sh_f[3 * NB + tid] = word_to_slot<wt>(g.s0);
+          *(park_t)&sh_f[4 * NB + tid] = word_to_slot<wt>(g.s1);
+        }
         const bool lq = light_branch && ltype == RTL_QUAD;
         const bool ls = (SC & kScLSphere) && light_branch && ltype == RTL_SPHERE;
         d3 c = ls ? ld3(L, 0) : p;
@@ -2736,6 +2802,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
           local = vfma(r2, ld3(L, 20), vfma(r1, ld3(L, 16), ld3(L, 4))) - p;
         }
         dir = local;
+        if constexpr (PARK) {
+          asm volatile("" ::"v"(dir.x), "v"(dir.y), "v"(dir.z));
+          g.s0 = slot_to_word<wt>(*(park_t)&sh_f[3 * NB + tid]);
+          g.s1 = slot_to_word<wt>(*(park_t)&sh_f[4 * NB + tid]);
+        }
       }
       wt mat_pdf, s_pdf;
       if (iso) {
@@ -2792,7 +2863,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const d3 perp = ratio * vfma(cos_t, normal, uu);
       const d3 refr = vfma(-sqrt_nr(fabs(1.0 - dot(perp, perp))), normal, perp);
       dir = refl ? reflect(uu, normal) : refr;
-      factor = to_w3(ld3(M, 0));  // attenuation = tint
+      factor = kWMirror ? mat_w() : to_w3(ld3(M, 0));  // attenuation = tint
     }
     p_next = p;
     d_next = dir;

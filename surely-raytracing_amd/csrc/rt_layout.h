@@ -134,8 +134,9 @@
 #define RTL_VOLUME_NEST 2
 #define RTL_END_WORDS 4
 
-/* material (20 words): [kind | flags(bit8: texture reads uv)][tex][0][0] d0-3 c.xyz, param,
- * d4-7 derived constants
+/* material (20 words): [kind | flags(bit8: texture reads uv, bit9: RTL_MATF_SOLID_W)][tex]
+ * [w.x][w.y] d0-3 c.xyz, param, d4-6 derived constants, d7 = [w.z][0] (w: the f32 weight mirror
+ * below)
  *   METAL: c = albedo, param = fuzz; DIELECTRIC: c = tint, param = ir, d4 = 1/ir,
  *   d5 / d6 = Schlick r0 for the front / back face ratio (material.rs:150-158, 166-191; the same
  *   IEEE divisions the reference performs per hit, done once on the host) */
@@ -151,8 +152,18 @@
 #define RTL_SC_ANY 0xffffffffu
 #define RTL_MAT_WORDS 20
 #define RTL_MATF_NEEDS_UV 0x100u
+/* f32 mirror of the colour a bounce multiplies the throughput by (a radiance weight, rt_kernel.h
+ * wt / w3): words [2], [3] and RTL_MAT_WZ (the low word of d7, which no kind uses) hold the bits of
+ * (float)x, (float)y, (float)z, the host cast = the device's v_cvt_f32_f64 (round to nearest even,
+ * denormals kept). METAL, DIELECTRIC: of c. LAMBERTIAN, ISOTROPIC, DIFFUSE_LIGHT over a SOLID
+ * texture: of that texture's colour, and RTL_MATF_SOLID_W is set: shading then takes albedo /
+ * emission from the material record and does not touch the texture table. Over any other texture
+ * the three words are 0 and the flag is clear. The f64 fields stay (first-hit AOVs, probes). */
+#define RTL_MATF_SOLID_W 0x200u
+#define RTL_MAT_WZ 18
 /* texture (12 words): [kind][a][b][c] d0-3
- *   SOLID: d0-2 color; CHECKER: d0 inv_scale, a even, b odd;
+ *   SOLID: d0-2 color, a b c = the f32 bits of d0-2 (as the material mirror above);
+ *   CHECKER: d0 inv_scale, a even, b odd;
  *   IMAGE: a width, b height, c byte offset into texels; NOISE: d0 scale, a perlin index */
 #define RTL_TEX_WORDS 12
 /* perlin table: ranvec 256 x float4 (x, y, z, 0; 4096 B: the turbulence is a radiance weight,

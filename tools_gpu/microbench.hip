@@ -1,5 +1,6 @@
 // Instruction-rate probes for the f64 path tracer (not shipped): f64/f32 FMA throughput and
-// dependent latency, v_rcp_f64 throughput, dependent scalar-load (s_load) latency.
+// dependent latency, v_rcp_f64 throughput, dependent scalar-load (s_load) latency, and the issue
+// cost of the path loop's conversions, 32-bit multiplies, f64 ldexp / rcp / rsq, select and move.
 // hipcc --offload-arch=gfx950 -O3 tools_gpu/microbench.hip -o build/microbench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -101,6 +102,49 @@ __global__ void __launch_bounds__(256) cmpsel64(double* out, double a, int iters
   if (s == 12345.678) out[0] = s;
 }
 
+// Issue cost of one instruction: 8 independent copies per round (each writes its own destination,
+// "+v" only to keep the eight apart, and reads loop-invariant sources, so nothing waits for a
+// result), 8 rounds per iteration.
+enum IssueOp { I_FMA64, I_CVT_F32_F64, I_CVT_F64_F32, I_CVT_F64_U32, I_MUL_LO_U32, I_MUL_HI_U32,
+               I_MAD_U64_U32, I_LDEXP_F64, I_RCP_F64, I_RSQ_F64, I_CNDMASK_B32, I_MOV_B64, I_CNDMASK_SGPR };
+template <int OP>
+__global__ void __launch_bounds__(256) issue(double* out, double a, unsigned b, int iters) {
+  double d[8], sd = a + threadIdx.x * 1e-3;
+  float f[8], sf = (float)sd;
+  unsigned u[8], su = b + threadIdx.x;
+  unsigned long long q[8];
+  const unsigned long long mask = 0x5555555555555555ull * (b | 1u);  // wave-uniform
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d[k] = sd + k, f[k] = sf + k, u[k] = su + k, q[k] = su + k;
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (OP == I_FMA64) asm volatile("v_fma_f64 %0, %1, %1, %1" : "+v"(d[k]) : "v"(sd));
+        if (OP == I_CVT_F32_F64) asm volatile("v_cvt_f32_f64 %0, %1" : "+v"(f[k]) : "v"(sd));
+        if (OP == I_CVT_F64_F32) asm volatile("v_cvt_f64_f32 %0, %1" : "+v"(d[k]) : "v"(sf));
+        if (OP == I_CVT_F64_U32) asm volatile("v_cvt_f64_u32 %0, %1" : "+v"(d[k]) : "v"(su));
+        if (OP == I_MUL_LO_U32) asm volatile("v_mul_lo_u32 %0, %1, %1" : "+v"(u[k]) : "v"(su));
+        if (OP == I_MUL_HI_U32) asm volatile("v_mul_hi_u32 %0, %1, %1" : "+v"(u[k]) : "v"(su));
+        if (OP == I_MAD_U64_U32)
+          asm volatile("v_mad_u64_u32 %0, vcc, %1, %1, %2" : "+v"(q[k]) : "v"(su), "v"(sd) : "vcc");
+        if (OP == I_LDEXP_F64) asm volatile("v_ldexp_f64 %0, %1, %2" : "+v"(d[k]) : "v"(sd), "v"(su));
+        if (OP == I_RCP_F64) asm volatile("v_rcp_f64 %0, %1" : "+v"(d[k]) : "v"(sd));
+        if (OP == I_RSQ_F64) asm volatile("v_rsq_f64 %0, %1" : "+v"(d[k]) : "v"(sd));
+        if (OP == I_CNDMASK_B32)
+          asm volatile("v_cndmask_b32 %0, %1, %2, vcc" : "+v"(u[k]) : "v"(su), "v"(sf));  // any mask
+        if (OP == I_CNDMASK_SGPR)  // the mask in an SGPR pair (VOP3) instead of VCC
+          asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "+v"(u[k]) : "v"(su), "v"(sf), "s"(mask));
+        if (OP == I_MOV_B64) asm volatile("v_mov_b64 %0, %1" : "+v"(d[k]) : "v"(sd));
+      }
+  }
+  double s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += d[k] + (double)f[k] + (double)u[k] + (double)q[k];
+  if (s == 12345.678) out[0] = s;
+}
+
 // dependent scalar loads: a wave-uniform pointer chase through a small table
 __global__ void __launch_bounds__(256) schase(const unsigned* __restrict__ tab, unsigned* out,
                                               int iters) {
@@ -170,6 +214,22 @@ int main() {
     report("v_xad_u32 8 chains", time_it([](int g) { int32op<1><<<g, 256>>>(g_u, 2654435761u, ITERS); }, grid), ITERS * 64.0);
     report("mul_u32_u24 8 chains", time_it([](int g) { int32op<2><<<g, 256>>>(g_u, 2654435761u, ITERS); }, grid), ITERS * 64.0);
     report("cmp f64+2 cndmask 8ch", time_it([](int g) { cmpsel64<<<g, 256>>>(g_d, 0.5, ITERS); }, grid), ITERS * 64.0);
+#define ISSUE(OP) \
+  report("issue " #OP, time_it([](int g) { issue<OP><<<g, 256>>>(g_d, 1.25, 40503u, ITERS); }, grid), ITERS * 64.0)
+    ISSUE(I_FMA64);
+    ISSUE(I_CVT_F32_F64);
+    ISSUE(I_CVT_F64_F32);
+    ISSUE(I_CVT_F64_U32);
+    ISSUE(I_MUL_LO_U32);
+    ISSUE(I_MUL_HI_U32);
+    ISSUE(I_MAD_U64_U32);
+    ISSUE(I_LDEXP_F64);
+    ISSUE(I_RCP_F64);
+    ISSUE(I_RSQ_F64);
+    ISSUE(I_CNDMASK_B32);
+    ISSUE(I_MOV_B64);
+    ISSUE(I_CNDMASK_SGPR);
+#undef ISSUE
   }
   return 0;
 }
