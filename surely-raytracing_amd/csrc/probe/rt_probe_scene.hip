@@ -7,17 +7,24 @@
 // the tables the way rt_scene_create does (the node array keeps its 256 bytes of padding), fills
 // the table fields of a TraceParams (everything else zero), launches one bounds-checked kernel with
 // one thread per record, the TraceParams by value as its first argument, copies back and frees
-// every buffer on every path. Synchronous HIP calls only; no state is kept between calls. Compiled
+// every buffer on every path. The two BVH entries (bvh_walks, world_hit_bvh) also set up what the
+// BVH kernels' launch sets up (rt_device.hip plan_lds, rt_kernel.h trace_body): kBlockBvh threads,
+// the compact trees copied to LDS offset 0 by the kernel before any walk, the per-lane walk
+// stacks after them. Synchronous HIP calls only; no state is kept between calls. Compiled
 // with the product's HIPFLAGS; no product code links this library.
 //
 // Return value: 0, a positive HIP error code, or a negative refusal that never reaches a kernel:
 // the flattener's status (include/rt_mi355x.h RT_ERR_*), or
-//   RTP_ERR_BVH     the scene has a BvhNode (with BVH = false, traverse steps over RTL_BVH records:
-//                   a silent miss must not pass for an answer)
+//   RTP_ERR_BVH     the scene has a BvhNode and the entry is not one of the BVH entries (with
+//                   BVH = false, traverse steps over RTL_BVH records: a silent miss must not pass
+//                   for an answer)
 //   RTP_ERR_NESTED  a ConstantMedium inside another one's boundary (not instantiated here)
 //   RTP_ERR_RECORD  a record carries an index that is not what the kernel would read it as: a
 //                   texture id outside the table, a node that is no top-level one-walk VOLUME
-//                   record, a frame that is neither -1 nor a transform record
+//                   record, a frame that is neither -1 nor a transform record; for the BVH
+//                   entries: a scene without a BvhNode, a node that is no top-level subtree root
+//                   with an ordered BVH and a compact copy, compact trees that fail the
+//                   flattener's host checks, an LDS need above 64 KB
 //   RTP_ERR_ARG     null pointers, a negative count
 //
 // The kernels call the product's functions and nothing else: no formula is restated here.
@@ -55,19 +62,50 @@ struct DevScene {
   }
 };
 
-// blob -> flattened tables + the record list; no HIP call
-int scene_flatten(const rt_scene_blob* blob, DevScene& S) {
+// The frame of every BVH record the top-level walk hands to the per-lane walker (traverse<UNI>'s
+// order: the world sequence, instances entered and left), by record word. BVH records sit in the
+// BVH region in front of the node array, so the memory-order scan below cannot tell their frame.
+std::vector<std::pair<uint32_t, int>> bvh_root_frames(const rtf::FlatScene& F) {
+  std::vector<std::pair<uint32_t, int>> roots;
+  const std::vector<uint32_t>& w = F.nodes;
+  uint32_t x = F.hdr.root;
+  int frame = -1;
+  for (size_t guard = 0; x + 4 <= F.hdr.n_rec_words && guard < w.size(); ++guard) {
+    const uint32_t ty = w[x] & 0xffu;
+    if (ty == RTL_END) break;
+    if (ty == RTL_BVH) roots.push_back({x, frame});
+    if (ty == RTL_TRANSLATE || ty == RTL_ROTATE_Y) frame = (int)x;
+    if (ty == RTL_EXIT) frame = (int)w[x + 2];
+    const bool next = ty == RTL_QUAD || ty == RTL_SPHERE || ty == RTL_TRANSLATE ||
+                      ty == RTL_ROTATE_Y || ty == RTL_EXIT;
+    x = next ? w[x + 3] : w[x + 1];
+  }
+  return roots;
+}
+
+// blob -> flattened tables + the record list; no HIP call. A BVH record is listed with its word 3
+// (its ordered BVH, 0 = none) in w2 and, as its frame, the one the top-level walk reaches it in,
+// -2 when that walk does not reach it (a node inside a subtree or inside a boundary).
+int scene_flatten(const rt_scene_blob* blob, DevScene& S, bool allow_bvh = false) {
   if (!blob) return RTP_ERR_ARG;
   std::string err;
   const int rc = rtf::flatten(blob, &S.F, &err);
   if (rc != RT_OK) return rc;
   const rtf::FlatScene& F = S.F;
-  if (F.hdr.has_bvh) return RTP_ERR_BVH;
+  if (F.hdr.has_bvh && !allow_bvh) return RTP_ERR_BVH;
   if (F.hdr.nested_volumes) return RTP_ERR_NESTED;
+  const std::vector<std::pair<uint32_t, int>> roots = bvh_root_frames(F);
   int frame = -1;
   for (size_t p = 0; p < F.hdr.n_rec_words; p += rtf::record_words(F.nodes[p])) {
     const uint32_t h = F.nodes[p], ty = h & 0xffu;
-    if (ty == RTL_BVH || ty == RTL_DUP) return RTP_ERR_BVH;
+    if ((ty == RTL_BVH || ty == RTL_DUP) && !allow_bvh) return RTP_ERR_BVH;
+    if (ty == RTL_BVH) {
+      int bf = -2;
+      for (const auto& r : roots)
+        if (r.first == p) bf = r.second;
+      S.recs.push_back({(uint32_t)p, ty, h >> 8, F.nodes[p + 3], bf});
+      continue;
+    }
     S.recs.push_back({(uint32_t)p, ty, h >> 8, p + 2 < F.nodes.size() ? F.nodes[p + 2] : 0u, frame});
     if (ty == RTL_TRANSLATE || ty == RTL_ROTATE_Y) frame = (int)p;
     if (ty == RTL_EXIT) frame = (int)F.nodes[p + 2];
@@ -138,7 +176,33 @@ hipError_t scene_upload(DevScene& S) {
   P.o_lights = (uint32_t)o_lig;
   P.o_loffs = (uint32_t)o_loff;
   P.o_perl = (uint32_t)o_perl;
+  // the BVH region stays in global memory (bvh_lds_words = 0), the compact trees go to LDS
+  // offset 0 with the walk stacks after them (bvh_lds_need checked the size)
+  P.bvh_words = F.hdr.bvh_words;
+  P.cbvh_lds_off = ~0u;
+  if (F.hdr.has_bvh && F.hdr.cbvh_words) {
+    P.cbvh_src = (const uint8_t*)(P.nodes + F.hdr.cbvh_word0);
+    P.cbvh_bytes = 4u * F.hdr.cbvh_words;
+    P.cbvh_lds_off = 0u;
+    P.stack_lds_off = P.cbvh_bytes;
+  }
   return hipSuccess;
+}
+
+// dynamic LDS of a BVH launch: the compact trees, then one stack per lane (stride blockDim.x)
+size_t bvh_lds_need(const rtf::FlatScene& F) {
+  return F.hdr.cbvh_words ? 4u * (size_t)F.hdr.cbvh_words + (size_t)F.hdr.cbvh_stack * kBlockBvh : 0u;
+}
+constexpr size_t kLdsDefault = 64u << 10;  // what a kernel gets without asking for more
+
+// what rt_scene_create checks before it uploads a BVH scene, and the launch's LDS need
+int bvh_host_checks(const rtf::FlatScene& F) {
+  if (!F.hdr.has_bvh) return RTP_ERR_RECORD;
+  if (F.hdr.cbvh_words && (F.hdr.cbvh_word0 % 4u || F.hdr.cbvh_words % 4u ||
+                           (size_t)F.hdr.cbvh_word0 + F.hdr.cbvh_words > F.nodes.size()))
+    return RTP_ERR_RECORD;
+  if (rtf::check_compact_trees(F.nodes, F.hdr, 0, 0).errors) return RTP_ERR_RECORD;
+  return bvh_lds_need(F) <= kLdsDefault ? 0 : RTP_ERR_RECORD;
 }
 
 template <class K>
@@ -151,14 +215,34 @@ __global__ void __launch_bounds__(kSceneBlock) scene_kernel(TraceParams P,
   K::apply(P, in + (size_t)i * K::IN, out + (size_t)i * K::OUT, arg);
 }
 
+// The BVH entries' kernel: the BVH kernels' block size, and their prologue's copy of the compact
+// trees into LDS (rt_kernel.h trace_body) before any lane walks
+template <class K>
+__global__ void __launch_bounds__(kBlockBvh) scene_kernel_bvh(TraceParams P,
+                                                              const double* __restrict__ in,
+                                                              double* __restrict__ out, int n,
+                                                              uint32_t arg) {
+  if (P.cbvh_lds_off != ~0u) {
+    const uint4* csrc = reinterpret_cast<const uint4*>(P.cbvh_src);
+    uint4* cdst = reinterpret_cast<uint4*>(rt_lds + P.cbvh_lds_off);
+    for (uint32_t k = threadIdx.x; k < P.cbvh_bytes / 16; k += blockDim.x) cdst[k] = csrc[k];
+  }
+  __syncthreads();
+  const int i = (int)(blockIdx.x * (unsigned)kBlockBvh + threadIdx.x);
+  if (i >= n) return;
+  K::apply(P, in + (size_t)i * K::IN, out + (size_t)i * K::OUT, arg);
+}
+
 // check(S, record) -> 0 or a refusal, on the host, for every record before anything is launched;
 // arg: a call-wide index (wave-uniform in the kernel), checked by the caller
-template <class K, class Check>
+template <class K, bool BVH = false, class Check>
 int scene_run(const rt_scene_blob* blob, const double* in, double* out, int n, uint32_t arg,
               Check check) {
   if (n < 0 || (n > 0 && (!in || !out))) return RTP_ERR_ARG;
   DevScene S;
-  int rc = scene_flatten(blob, S);
+  int rc = scene_flatten(blob, S, BVH);
+  if (rc) return rc;
+  if (BVH) rc = bvh_host_checks(S.F);
   if (rc) return rc;
   rc = check(S, (const double*)nullptr);  // the call-wide argument
   for (int i = 0; i < n && !rc; ++i) rc = check(S, in + (size_t)i * K::IN);
@@ -172,8 +256,14 @@ int scene_run(const rt_scene_blob* blob, const double* in, double* out, int n, u
   if (e == hipSuccess) e = hipMemcpy(din, in, ib, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(dout, 0, ob);
   if (e == hipSuccess) {
-    const unsigned blocks = ((unsigned)n + kSceneBlock - 1u) / kSceneBlock;
-    scene_kernel<K><<<dim3(blocks), dim3(kSceneBlock), 0, 0>>>(S.P, din, dout, n, arg);
+    if constexpr (BVH) {
+      const unsigned blocks = ((unsigned)n + kBlockBvh - 1u) / kBlockBvh;
+      scene_kernel_bvh<K><<<dim3(blocks), dim3(kBlockBvh), bvh_lds_need(S.F), 0>>>(S.P, din, dout,
+                                                                                   n, arg);
+    } else {
+      const unsigned blocks = ((unsigned)n + kSceneBlock - 1u) / kSceneBlock;
+      scene_kernel<K><<<dim3(blocks), dim3(kSceneBlock), 0, 0>>>(S.P, din, dout, n, arg);
+    }
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -224,6 +314,78 @@ struct K_world_hit_t {
                                                uint32_t) {
     one<false>(P, in, out);
     one<true>(P, in, out + 7);
+  }
+};
+
+// The same query through the BVH kernels' walker (traverse<..., UNI, BVH = true, VOLB, VOLI>):
+// bvh_subtree's ordered walk from LDS, its ballot and the flagged lanes' re-walk in the product
+// build, the reference tree in the COUNT build (which always carries the two-walk interpreter).
+template <bool VOL, bool VOLB, bool VOLI>
+struct K_world_hit_bvh_t {
+  static constexpr int IN = 13, OUT = 14;
+  template <bool COUNT>
+  static __device__ __forceinline__ void one(const TraceParams& P, const double* in, double* out) {
+    Ctr<COUNT> C;
+    Rng g = rng_seed((uint32_t)in[9], (uint32_t)in[10], (uint32_t)in[11], (uint32_t)in[12]);
+    const d3 o = in3(in), d = in3(in + 3);
+    double t = 0.0;
+    uint32_t hn = 0u;
+    int hf = -1;
+    const bool h = traverse<true, COUNT, VOL, true, true, VOLB, (COUNT || VOLI)>(
+        P, P.root, ~0u, o, d, in[6], o, d, -1, in[7], in[8], t, hn, hf, g, C);
+    out[0] = h ? 1.0 : 0.0, out[1] = t;
+    out[2] = h ? (double)hn : -1.0, out[3] = h ? (double)hf : -1.0;
+    out[4] = h ? (double)P.nodes[hn + 2] : -1.0;
+    out[5] = (double)g.s0, out[6] = (double)g.s1;
+  }
+  static __device__ __forceinline__ void apply(const TraceParams& P, const double* in, double* out,
+                                               uint32_t) {
+    one<false>(P, in, out);
+    one<true>(P, in, out + 7);
+  }
+};
+
+// ---------------------------------------------------------------- the BVH walkers, ray by ray
+// arg: a top-level BVH subtree root (frame -1) with an ordered BVH and a compact copy. in: o3, d3,
+// time, tmin, tmax. One thread runs the ray through cbvh_walk (the compact tree in LDS), obvh_walk
+// (the octant streams in global memory) and the reference-order traverse over [node, skip). out,
+// once with MAIN = true and once with MAIN = false (the ConstantMedium boundary's instantiation;
+// hit node -1): per walk hit, t (tmax on a miss), hit node, and the ordered walks' tie flag:
+// [cbvh 4][obvh 4][reference 3].
+struct K_bvh_walks {
+  static constexpr int IN = 9, OUT = 22;
+  template <bool MAIN>
+  static __device__ __forceinline__ void pass(const TraceParams& P, uint32_t node, uint4 h, uint4 hd,
+                                              const double* in, double* out) {
+    const d3 o = in3(in), d = in3(in + 3);
+    const double tm = in[6], tmin = in[7], tmax = in[8];
+    auto put = [&](double* p, bool hit, double t, uint32_t hn) {
+      p[0] = hit ? 1.0 : 0.0, p[1] = hit ? t : tmax, p[2] = hit && MAIN ? (double)hn : -1.0;
+    };
+    double t = tmax;
+    uint32_t hn = 0u;
+    int hf = -1;
+    bool fl = false;
+    bool hit = cbvh_walk<MAIN>(P, hd, o, d, tm, -1, tmin, tmax, t, hn, hf, fl);
+    put(out, hit, t, hn);
+    out[3] = fl ? 1.0 : 0.0;
+    t = tmax, hn = 0u, fl = false;
+    hit = obvh_walk<MAIN>(P, h.w, o, d, tm, -1, tmin, tmax, t, hn, hf, fl);
+    put(out + 4, hit, t, hn);
+    out[7] = fl ? 1.0 : 0.0;
+    Ctr<false> C;
+    Rng g = rng_seed(0u, 0u, 0u, 0u);
+    t = tmax, hn = 0u;
+    hit = traverse<MAIN, false, false, false, true>(P, node, h.y, o, d, tm, o, d, -1, tmin, tmax, t,
+                                                    hn, hf, g, C);
+    put(out + 8, hit, t, hn);
+  }
+  static __device__ __forceinline__ void apply(const TraceParams& P, const double* in, double* out,
+                                               uint32_t node) {
+    const uint4 h = ld4u((kptr)P.nodes + node);     // [hdr][skip][first child][ordered BVH]
+    const uint4 hd = ld4u((gptr)P.nodes + h.w);     // [n_entries][cbvh block][root ref][streams]
+    pass<true>(P, node, h, hd, in, out);
+    pass<false>(P, node, h, hd, in, out + 11);
   }
 };
 
@@ -322,6 +484,9 @@ SCENE_PROBE(frame, 13, 12)
 SCENE_PROBE(volume_bounds, 7, 8)
 SCENE_PROBE(light_pdf, 7, 2)
 SCENE_PROBE(tex_value, 6, 6)
+typedef K_world_hit_bvh_t<false, false, true> K_world_hit_bvh;
+SCENE_PROBE(world_hit_bvh, 13, 14)
+SCENE_PROBE(bvh_walks, 9, 22)
 }  // namespace
 
 RTP_API int rtp_world_hit(const rt_scene_blob* blob, const double* in, double* out, int n) {
@@ -330,6 +495,40 @@ RTP_API int rtp_world_hit(const rt_scene_blob* blob, const double* in, double* o
   if (rc) return rc;
   if (S.F.hdr.has_volume) return scene_run<K_world_hit_t<true>>(blob, in, out, n, 0u, no_check);
   return scene_run<K_world_hit_t<false>>(blob, in, out, n, 0u, no_check);
+}
+
+// The kernel variant rt_device.hip / rtj::product_flags choose for the scene: VOL with a
+// ConstantMedium or an Isotropic material, VOLB unless every volume sits outside the BVH subtrees,
+// VOLI unless those are all one-walk spheres (the COUNT half keeps the interpreter).
+RTP_API int rtp_world_hit_bvh(const rt_scene_blob* blob, const double* in, double* out, int n) {
+  DevScene S;
+  const int rc = scene_flatten(blob, S, true);
+  if (rc) return rc;
+  const rtl_scene_header& H = S.F.hdr;
+  if (!H.has_bvh) return RTP_ERR_RECORD;
+  const bool vol = (H.has_volume | H.has_isotropic) != 0;
+  const bool novolb = vol && !H.volume_in_bvh;
+  if (!vol) return scene_run<K_world_hit_bvh_t<false, false, true>, true>(blob, in, out, n, 0u, no_check);
+  if (!novolb) return scene_run<K_world_hit_bvh_t<true, true, true>, true>(blob, in, out, n, 0u, no_check);
+  if (H.volumes_one_walk_spheres)
+    return scene_run<K_world_hit_bvh_t<true, false, false>, true>(blob, in, out, n, 0u, no_check);
+  return scene_run<K_world_hit_bvh_t<true, false, true>, true>(blob, in, out, n, 0u, no_check);
+}
+
+RTP_API int rtp_bvh_walks(const rt_scene_blob* blob, int node, const double* in, double* out,
+                          int n) {
+  return scene_run<K_bvh_walks, true>(blob, in, out, n, (uint32_t)node,
+                                      [node](const DevScene& S, const double* r) {
+    if (r) return 0;
+    const Rec* x = find_rec(S, (double)node);
+    if (!x || x->type != RTL_BVH || x->frame != -1 || x->w2 == 0u) return RTP_ERR_RECORD;
+    // the ordered BVH's header and streams inside the node array, a compact block staged
+    const std::vector<uint32_t>& w = S.F.nodes;
+    const size_t ob = x->w2;
+    if (ob < S.F.hdr.n_rec_words || ob + 8 > w.size() || w[ob + 1] == ~0u) return RTP_ERR_RECORD;
+    if (w[ob + 1] >= 4u * S.F.hdr.cbvh_words) return RTP_ERR_RECORD;
+    return ob + w[ob + 3] + (size_t)64 * w[ob] <= w.size() ? 0 : RTP_ERR_RECORD;
+  });
 }
 
 RTP_API int rtp_frame(const rt_scene_blob* blob, const double* in, double* out, int n) {
@@ -365,12 +564,15 @@ RTP_API int rtp_tex_value(const rt_scene_blob* blob, const double* in, double* o
 
 // The records of the flattened world sequence in memory order, so a test can name a frame or a
 // VOLUME record and tell which primitive a hit node is: rows of [word, type, header word 0 >> 8,
-// word 2 (material, chain length or parent frame), enclosing frame]. Returns the number of
-// records (at most `cap` rows are written) or a refusal. No GPU is touched.
+// word 2 (material, chain length or parent frame), enclosing frame]. A scene with a BvhNode is
+// listed too (this entry launches nothing): a BVH record's fourth column is its ordered BVH's word
+// offset (0 = none, the reference tree is walked) and its frame is the one the top-level walk
+// reaches it in, -2 for a node that walk does not reach. Returns the number of records (at most
+// `cap` rows are written) or a refusal. No GPU is touched.
 RTP_API int rtp_scene_records(const rt_scene_blob* blob, double* out, int cap) {
   if (cap < 0 || (cap > 0 && !out)) return RTP_ERR_ARG;
   DevScene S;
-  const int rc = scene_flatten(blob, S);
+  const int rc = scene_flatten(blob, S, true);
   if (rc) return rc;
   for (size_t i = 0; i < S.recs.size() && i < (size_t)cap; ++i) {
     const Rec& r = S.recs[i];

@@ -1272,7 +1272,8 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
 // candidate wins; away from ties that is the record the reference order returns. The lane is
 // flagged (the caller re-walks the reference tree in the reference order) when its result could
 // depend on the order: a candidate within kTieRel (relative) of the running closest t (which
-// starts at the caller's tmax), or a winner within kTieRel of tmin. Boxes are padded bounds and
+// starts at the caller's tmax), a winner within kTieRel of tmin, or a winner whose own test was
+// decided by rounding (obvh_far). Boxes are padded bounds and
 // the slab test keeps every box whose entry is <= closest * (1 + kTieRel), so no candidate the
 // flag logic must see is culled.
 constexpr double kTieRel = 0x1p-30;
@@ -1394,6 +1395,37 @@ __device__ __forceinline__ void obvh_leaf(const gptr N, uint32_t rec, d3 o, d3 d
   }
 }
 
+// Whether the winning record's own test was decided by rounding, once per walk that hits. The
+// reference tree culls with f64 boxes, the ordered walks with outward-rounded f32 ones, so they
+// also test leaves the reference never reaches. That is harmless while a leaf test agrees with
+// its box (a ray that misses the box misses the primitive inside it), but a ray that starts
+// further from a primitive than about 2^26 of its size has a leaf test made of rounding noise (a
+// sphere's r^2 drops below an ulp of the discriminant's terms; a quad's planar coordinates are off
+// by more than the quad), which can report a hit the reference's boxes exclude. Such a winner
+// flags the lane, and the reference order decides. The thresholds leave the test's noise at or
+// below 2^-12 of the primitive: a sphere when |o - c|^2 <= 2^40 r^2; a quad when the planar
+// coordinates a = pq.A, b = pq.B, of range [0, 1] over the quad, carry at most
+// 2^-52 (|o| + t |d|) (|A| + |B|) <= 2^-12 of error. No camera or scattered ray of a scene whose
+// primitives are not smaller than 2^-20 of its extent comes near either.
+__device__ __forceinline__ bool obvh_far(const gptr N, uint32_t rec, d3 o, d3 d, double tm,
+                                         double t) {
+  // Both forms' loads are issued before the record's type is known: one round trip, not two. (On
+  // a sphere record the quad's words are the following records or the allocation's 256-byte
+  // tail, as in obvh_leaf's batch loop.)
+  const gptr X = N + rec;
+  const gptr G = X + RTL_QUAD_GEN;
+  const uint32_t h0 = X[0];
+  const d3 c = ld3(X, 0), cv = ld3(X, 4);
+  const double rad = ldd(X, 3);
+  const d3 A = ld3(G, 8), B = ld3(G, 12);
+  const d3 oc = o - ((h0 & RTL_SPHERE_MOVING) ? vfma(tm, cv, c) : c);
+  const bool far_s = !(dot(oc, oc) <= 0x1p40 * (rad * rad));
+  const double s = fabs(o.x) + fabs(o.y) + fabs(o.z) + fabs(t) * (fabs(d.x) + fabs(d.y) + fabs(d.z));
+  const double w = fabs(A.x) + fabs(A.y) + fabs(A.z) + fabs(B.x) + fabs(B.y) + fabs(B.z);
+  const bool far_q = !(s * w <= 0x1p40);
+  return (h0 & 0xffu) == RTL_SPHERE ? far_s : far_q;
+}
+
 template <bool MAIN>
 __device__ bool obvh_walk(const TraceParams& P, uint32_t ob, d3 o, d3 d, double tm, int frame,
                           double tmin, double tmax, double& t_out, uint32_t& hit_node,
@@ -1475,6 +1507,7 @@ __device__ bool obvh_walk(const TraceParams& P, uint32_t ob, d3 o, d3 d, double 
   }
   flag = ((tie_at >= 0.0) & (fabs(tie_at - closest) <= closest * (2.0 * kTieRel))) |
          (hit & (closest <= tmin * (1.0 + kTieRel)));
+  if (hit && !flag) flag = obvh_far(N, hn, o, d, tm, closest);
 #ifdef RT_PROF
   {
     const unsigned long long dt = __builtin_readcyclecounter() - pf_t0;
@@ -1701,6 +1734,7 @@ __device__ bool cbvh_walk_t(const TraceParams& P, uint4 hd, d3 o, d3 d, double t
   }
   flag = ((second < kInf) & (second <= closest * (1.0 + 3.0 * kTieRel))) |
          (hit & (closest <= tmin * (1.0 + kTieRel)));
+  if (hit && !flag) flag = obvh_far(N, hn, o, d, tm, closest);  // as obvh_walk: the same flag
 #ifdef RT_PROF
   {
     const unsigned long long dt = __builtin_readcyclecounter() - pf_t0;

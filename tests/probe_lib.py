@@ -38,12 +38,14 @@ PERLIN_BYTES = 4096 + 768  # rt_layout.h RTL_PERLIN_BYTES
 SCENE_PROBES = {
     "world_hit": (13, 14), "frame": (13, 12), "volume_bounds": (7, 8),  # volume_bounds: plus the node
     "light_pdf": (7, 2), "tex_value": (6, 6),
+    "world_hit_bvh": (13, 14), "bvh_walks": (9, 22),  # bvh_walks: plus the node
 }
+NODE_PROBES = ("volume_bounds", "bvh_walks")  # these take a record's word offset after the blob
 # refusals of the scene probes (negative; a positive code is a HIP error): rt_probe_scene.hip
 ERR_ARG, ERR_BVH, ERR_NESTED, ERR_RECORD = -100, -101, -102, -103
 # rt_layout.h record types, as scene_records reports them
-RTL_END, RTL_QUAD, RTL_SPHERE, RTL_TRANSLATE, RTL_ROTATE_Y, RTL_EXIT, RTL_VOLUME, RTL_QUADS = (
-    0, 1, 2, 4, 5, 6, 7, 9)
+RTL_END, RTL_QUAD, RTL_SPHERE, RTL_BVH, RTL_TRANSLATE, RTL_ROTATE_Y, RTL_EXIT, RTL_VOLUME, RTL_QUADS, RTL_DUP = (
+    0, 1, 2, 3, 4, 5, 6, 7, 9, 10)
 RTL_XFORM_LONG = 1  # header flag bits as scene_records reports them (header word 0 >> 8)
 RTL_VOLF_SPHERE, RTL_VOLF_QUADS = 1, 2
 
@@ -69,7 +71,8 @@ def lib() -> C.CDLL:
             f = getattr(L, f"rtp_{name}")
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.rtp_volume_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        for name in NODE_PROBES:
+            getattr(L, f"rtp_{name}").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.rtp_scene_records.restype = C.c_int
         L.rtp_scene_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
@@ -124,7 +127,7 @@ def _scene_call(name, blob, x, *lead):
 
 def scene_run(name: str, blob, x) -> np.ndarray:
     """scene probe `name` of the serialised scene `blob` on the records x -> [n, OUT] float64."""
-    assert name != "volume_bounds"
+    assert name not in NODE_PROBES
     return _scene_call(name, blob, x)
 
 
@@ -133,9 +136,19 @@ def volume_bounds(blob, node: int, rays7) -> np.ndarray:
     return _scene_call("volume_bounds", blob, rays7, int(node))
 
 
+def bvh_walks(blob, node: int, rays9) -> np.ndarray:
+    """cbvh_walk, obvh_walk and the reference-order traverse of the top-level BVH subtree root at
+    `node` on the records (o3, d3, time, tmin, tmax) -> [n, 22]: with MAIN = true, then with MAIN =
+    false (hit node -1): [hit, t, hit node, tie flag] of the LDS walk, of the streams walk, then
+    [hit, t, hit node] of the reference-order walk."""
+    return _scene_call("bvh_walks", blob, rays9, int(node))
+
+
 def scene_records(blob) -> np.ndarray:
     """The flattened world's records in memory order -> [n, 5] int64: word, type, header word 0 >> 8,
-    word 2, enclosing frame. Needs no GPU."""
+    word 2, enclosing frame. A BVH record (they come first) has its ordered BVH's word offset (0 =
+    none) in column 3 and as its frame the one the top-level walk reaches it in, -2 for a node that
+    walk does not reach (inside a subtree or a boundary). Needs no GPU."""
     cap = 4096
     out = np.zeros((cap, 5), np.float64)
     n = lib().rtp_scene_records(C.cast(blob.ref(), C.c_void_p), out.ctypes.data, cap)

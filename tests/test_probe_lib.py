@@ -22,7 +22,7 @@ def test_probe_library_builds_loads_and_exports_every_bound_symbol():
     assert P.PROBE_SO.exists()
     lib = P.lib()
     raw = C.CDLL(str(P.PROBE_SO))
-    assert len(P.PROBES) >= 32 and len(P.SCENE_PROBES) >= 5
+    assert len(P.PROBES) >= 32 and len(P.SCENE_PROBES) >= 7
     assert len(P.symbols()) == len(P.PROBES) + len(P.SCENE_PROBES) + 1
     for sym in P.symbols():
         assert getattr(raw, sym) is not None and getattr(lib, sym).restype is C.c_int, sym
@@ -93,7 +93,10 @@ def test_scene_records_and_host_refusals():
 
     ray = [0.0] * 13
     assert refused(P.scene_run, "world_hit", _blob(bvh=True), ray) == P.ERR_BVH
-    assert refused(P.scene_records, _blob(bvh=True)) == P.ERR_BVH
+    for name in ("frame", "light_pdf", "tex_value"):  # every entry that is not a BVH entry
+        assert refused(P.scene_run, name, _blob(bvh=True), [0.0] * P.SCENE_PROBES[name][0]) == P.ERR_BVH
+    vol0 = int(vol[0, 0])
+    assert refused(P.volume_bounds, _blob(bvh=True), vol0, [0.0] * 7) == P.ERR_BVH
     assert refused(P.scene_run, "world_hit", _blob(nested=True), ray) == P.ERR_NESTED
     quad = int(recs[recs[:, 1] == P.RTL_QUAD][0, 0])
     for frame in (quad, tr + 4, -2, 1 << 20, 0.5):  # not a transform record
@@ -104,3 +107,88 @@ def test_scene_records_and_host_refusals():
         assert refused(P.scene_run, "tex_value", blob, [tex] + [0.0] * 5) == P.ERR_RECORD
     # one bad record among good ones refuses the whole call
     assert refused(P.scene_run, "frame", blob, [[-1.0] + [0.0] * 12, [quad] + [0.0] * 12]) == P.ERR_RECORD
+
+
+def _bvh_blob(kind):
+    """`two`: a top-level BVH of 6 spheres and quads, an instance of a BVH of 4 spheres, a plain
+    sphere. `instance_leaf`: a BVH with a Translate among its leaves (no ordered BVH).
+    `deep`: 48 spheres in a row, each twice the last: a compact tree 22 levels deep, whose 768 walk
+    stacks of 88 bytes need more than 64 KB of LDS."""
+    sc = rt.Scene(5)
+    m = sc.lambertian((0.5, 0.5, 0.5))
+    if kind == "two":
+        a = [sc.sphere((2.0 * k, 0, 0), 0.5, m) for k in range(4)] + [
+            sc.quad((0, 2, 0), (1, 0, 0), (0, 0, 1), m), sc.quad((3, 2, 0), (1, 0.5, 0), (0, 0, 1), m)]
+        b = [sc.sphere((0, 0, 2.0 * k), 0.5, m) for k in range(4)]
+        objs = [sc.create_bvh(sc.hittable_list(*a)),
+                sc.translate(sc.rotate_y(sc.create_bvh(sc.hittable_list(*b)), 30.0), (0, 5, 0)),
+                sc.sphere((0, -3, 0), 1.0, m)]
+    elif kind == "instance_leaf":
+        a = [sc.sphere((2.0 * k, 0, 0), 0.5, m) for k in range(3)]
+        a.append(sc.translate(sc.sphere((0, 0, 0), 0.5, m), (0, 3, 0)))
+        objs = [sc.create_bvh(sc.hittable_list(*a))]
+    elif kind == "deep":
+        a, x = [], 0.0
+        for k in range(48):
+            r = 0.01 * 2.0 ** k
+            x += 2.5 * r
+            a.append(sc.sphere((x, 0, 0), r, m))
+            x += 2.5 * r
+        objs = [sc.create_bvh(sc.hittable_list(*a))]
+    return sc.serialize(sc.hittable_list(*objs), None)
+
+
+def test_bvh_entries_records_and_host_refusals():
+    """No GPU: scene_records lists a BVH scene (the other entries keep refusing it), and the two
+    BVH entries refuse before any launch a scene without a BvhNode, a node that is no top-level
+    subtree root with an ordered BVH (a leaf, a nested BVH node, a root inside an instance, a root
+    whose leaves hold an instance), and an LDS need above 64 KB."""
+    def refused(fn, *a):
+        with pytest.raises(P.ProbeRefused) as e:
+            fn(*a)
+        return e.value.code
+
+    blob = _bvh_blob("two")
+    recs = P.scene_records(blob)
+    bvh = recs[recs[:, 1] == P.RTL_BVH]
+    assert len(bvh) >= 5 + 3 and (bvh[:, 0] == 16 * np.arange(len(bvh))).all()  # the BVH region, in front
+    tops = bvh[bvh[:, 4] == -1]
+    ry = recs[recs[:, 1] == P.RTL_ROTATE_Y][0]
+    inst = bvh[bvh[:, 4] == ry[0]]
+    assert len(tops) == 1 and len(inst) == 1 and (bvh[:, 4] == -2).sum() == len(bvh) - 2
+    assert tops[0, 3] > recs[-1, 0] and inst[0, 3] > tops[0, 3]  # ordered BVHs follow the records
+    assert (bvh[bvh[:, 4] == -2, 3] == 0).all()  # only a subtree root has one
+    types = recs[:, 1].tolist()
+    # a span of one leaf is a BvhNode of that leaf twice: a DUP record in front of the second copy
+    n_leaf = types.count(P.RTL_SPHERE) + types.count(P.RTL_QUAD)
+    assert n_leaf == 11 + types.count(P.RTL_DUP) and types.count(P.RTL_QUAD) >= 2
+    sph = recs[recs[:, 1] == P.RTL_SPHERE]
+    assert (sph[:, 4] == ry[0]).sum() >= 4 and sph[-1, 4] == -1  # the instance's leaves; the plain one
+    ray9, ray13 = [0.0] * 9, [0.0] * 13
+    top, sphere = int(tops[0, 0]), int(recs[recs[:, 1] == P.RTL_SPHERE][0, 0])
+    nested = int(bvh[bvh[:, 4] == -2][0, 0])
+    for node in (sphere, nested, int(inst[0, 0]), top + 4, int(tops[0, 3]), -1, 1 << 20):
+        assert refused(P.bvh_walks, blob, node, ray9) == P.ERR_RECORD, node
+    assert refused(P.scene_run, "world_hit", blob, ray13) == P.ERR_BVH
+    # no record, no launch: the accepted node and scene pass every host check
+    assert P.bvh_walks(blob, top, np.zeros((0, 9))).shape == (0, 22)
+    assert P.scene_run("world_hit_bvh", blob, np.zeros((0, 13))).shape == (0, 14)
+    # a scene without a BvhNode
+    assert refused(P.scene_run, "world_hit_bvh", _blob(), ray13) == P.ERR_RECORD
+    assert refused(P.bvh_walks, _blob(), 0, ray9) == P.ERR_RECORD
+    assert refused(P.scene_run, "world_hit_bvh", _blob(nested=True), ray13) == P.ERR_NESTED
+    # an instance among the leaves: listed, no ordered BVH, so only world_hit_bvh takes it
+    blob = _bvh_blob("instance_leaf")
+    recs = P.scene_records(blob)
+    bvh = recs[recs[:, 1] == P.RTL_BVH]
+    assert (bvh[:, 3] == 0).all() and bvh[0, 4] == -1
+    assert refused(P.bvh_walks, blob, int(bvh[0, 0]), ray9) == P.ERR_RECORD
+    assert P.scene_run("world_hit_bvh", blob, np.zeros((0, 13))).shape == (0, 14)
+    # compact tree + 768 walk stacks above 64 KB
+    blob = _bvh_blob("deep")
+    chk = rt.lds_check(blob, 0, 0, 1)
+    assert chk["cbvh_bytes"] + chk["cbvh_stack"] * 768 > 65536 and chk["errors"] == 0, chk
+    recs = P.scene_records(blob)
+    assert recs[0, 1] == P.RTL_BVH and recs[0, 3] != 0 and recs[0, 4] == -1
+    assert refused(P.bvh_walks, blob, 0, ray9) == P.ERR_RECORD
+    assert refused(P.scene_run, "world_hit_bvh", blob, ray13) == P.ERR_RECORD

@@ -93,6 +93,11 @@ def _parse(s, pos):
             k, pos = _parse(s, pos)
             kids.append(k)
         return dict(tag=tag, kids=kids), pos
+    if tag == OBJ_BVH:  # [tag, bbox6], then left and right
+        left, pos = _parse(s, pos + 7)
+        right, pos = _parse(s, pos)
+        # a span of one leaf is a BvhNode of that leaf twice (hittable.rs:161-162): one candidate
+        return dict(tag=tag, kids=[left, right], dup=left == right), pos
     if tag == OBJ_SPHERE:
         return dict(tag=tag, mat=int(s[pos + 1]), moving=int(s[pos + 2]), c=v3(pos + 3), r=f(pos + 6),
                     cv=v3(pos + 7)), pos + 16
@@ -160,7 +165,8 @@ def _cross(a, b):
 
 class _Ctx:
     """One ray's exact evaluation: `guard` collects every decision within the band; `u` is the
-    ray's first draw, `draws` how many ConstantMedium draws the walk takes."""
+    ray's first draw (or the list of its first draws, for a world with several mediums), `draws` how
+    many ConstantMedium draws the walk takes."""
 
     def __init__(self, tm, u=None):
         self.tm, self.u, self.guard, self.draws = Fr(tm), u, False, 0
@@ -212,6 +218,13 @@ def _sphere_x(cx, nd, o, d, tmin, tmax):
     return None
 
 
+def _bvh_leaves(nd):
+    """The leaves of a BvhNode in blob order, a duplicated span-1 leaf once."""
+    if nd["tag"] != OBJ_BVH:
+        return [nd]
+    return _bvh_leaves(nd["kids"][0]) + ([] if nd["dup"] else _bvh_leaves(nd["kids"][1]))
+
+
 def _hit_x(cx, nd, o, d, tmin, tmax):
     """Object::hit exactly -> (t, the primitive's node) or None (hittable.rs, transform.rs,
     constant_medium.rs in the reference's order)."""
@@ -223,6 +236,15 @@ def _hit_x(cx, nd, o, d, tmin, tmax):
             if h:
                 best, closest = h, h[0]
         return best
+    if tag == OBJ_BVH:
+        # In exact arithmetic a BvhNode is the list of its leaves: the closest candidate. The
+        # reference walks them in its tree's order, not the list's, which decides only between
+        # candidates that tie: the guard band, whenever the two smallest lie within it.
+        cands = [h for h in (_hit_x(cx, k, o, d, tmin, tmax) for k in _bvh_leaves(nd)) if h]
+        cands.sort(key=lambda h: _m(h[0]))
+        if len(cands) > 1:
+            cx.near(cands[0][0], cands[1][0])
+        return cands[0] if cands else None
     if tag == OBJ_QUAD:
         t = _quad_x(cx, nd, o, d, tmin, tmax)
         return None if t is None else (t, nd)
@@ -257,8 +279,9 @@ def _hit_x(cx, nd, o, d, tmin, tmax):
             t1 = Fr(0)
         ln = mp.sqrt(_m(_dot(d, d)))
         inside = (_m(t2) - _m(t1)) * ln
+        u = cx.u[cx.draws] if isinstance(cx.u, (list, tuple)) else cx.u  # one draw per medium reached
         cx.draws += 1
-        dist = M(nd["nid"]) * mp.log(M(cx.u))
+        dist = M(nd["nid"]) * mp.log(M(u))
         cx.near(dist, inside)
         if dist > inside:
             return None
