@@ -132,7 +132,10 @@ typedef struct rt_camera {
 #define RT_FLAG_OVERWRITE 0x1u             /* accum = sums instead of accum += sums          */
 #define RT_FLAG_COUNT_OPS 0x2u             /* run the op-counting build, fill rt_stats.ops   */
 #define RT_FLAG_SEMANTICS_REFERENCE 0x4u   /* exact reference semantics: empty lights -> error, */
-                                           /* Isotropic scattering_pdf = 0 */
+                                           /* Isotropic scattering_pdf = 0. */
+/* S9: a path whose throughput is exactly zero in all channels and that carries no special value
+ * ends with radiance 0; the reference goes on and returns NaN if a later bounce has a zero or NaN
+ * pdf; RT_FLAG_SEMANTICS_REFERENCE keeps the reference's behaviour. */
 #define RT_FLAG_INTERPRETER 0x8u           /* product render with the interpreter walker, not the */
                                            /* scene-specialised kernel (same image, bit for bit)  */
 #define RT_FLAG_REFERENCE_BVH 0x10u        /* product render walks BVH subtrees in the reference's */

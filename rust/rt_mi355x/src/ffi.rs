@@ -45,6 +45,10 @@ pub const RT_TEX_NOISE: i64 = 4;
 // render flags
 pub const RT_FLAG_OVERWRITE: u32 = 0x1;
 pub const RT_FLAG_COUNT_OPS: u32 = 0x2;
+/// Exact reference semantics: empty lights -> error, Isotropic scattering_pdf = 0 (S1/S2).
+/// S9: a path whose throughput is exactly zero in all channels and that carries no special value
+/// ends with radiance 0; the reference goes on and returns NaN if a later bounce has a zero or NaN
+/// pdf; RT_FLAG_SEMANTICS_REFERENCE keeps the reference's behaviour.
 pub const RT_FLAG_SEMANTICS_REFERENCE: u32 = 0x4;
 pub const RT_FLAG_INTERPRETER: u32 = 0x8;
 pub const RT_FLAG_REFERENCE_BVH: u32 = 0x10;

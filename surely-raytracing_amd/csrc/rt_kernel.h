@@ -2117,6 +2117,8 @@ __device__ wt light_pdf(const TraceParams& P, d3 origin, d3 dir, double cos_sl0,
 //   +inf otherwise (x / 0 with x > 0; a later such bounce inside the sub-path resolves the same
 //        way, and the finite radiance gathered before it is absorbed by the inf / NaN).
 // Radiance is never negative (attenuations, emission and PDFs are >= 0), so no -inf arises.
+// A prefix throughput that is 0 in ALL channels no longer reaches such a bounce: the path ended
+// with radiance 0 before it (semantics S9, trace_body ZCUT), unless RT_FLAG_SEMANTICS_REFERENCE.
 constexpr uint32_t RT_XS_ON = 8u;
 __device__ __forceinline__ uint32_t xs_nan_bits(w3 c, w3 beta) {
   const bool nx = !(c.x != 0.0) | !(beta.x != 0.0);  // 0 or NaN
@@ -2312,6 +2314,18 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   // the radiance shares the factor's slots: the six slots per lane cost no LDS over sh_f + sh_le.
   constexpr bool DEFER = !COUNT && LDSF && Trav::kLpdfDefer;
   constexpr int kLpPend = (int)(16u << 24);  // above RT_XS_*
+  // Zero throughput (semantics S9): once beta is exactly 0 in all three channels and no special
+  // value is pending, everything the path still gathers is 0 * X = +0, so the product kernels end
+  // the sample there with radiance 0 (the commit below). The counting build runs the path on, for
+  // the oracle's op counts, and marks the lane dead instead: end_sample then writes the same 0.
+  // RT_FLAG_SEMANTICS_REFERENCE switches both off; -DRT_NO_ZERO_CUT compiles them out (A/B).
+#ifdef RT_NO_ZERO_CUT
+  constexpr bool ZCUT = false;
+#else
+  constexpr bool ZCUT = true;
+#endif
+  constexpr int kXsMask = (int)(15u << 24);  // RT_XS_ON and the three NaN bits
+  constexpr int kDead = (int)(32u << 24);    // COUNT: the sample's radiance is 0 (above kLpPend)
   constexpr int LE0 = DEFER ? 0 : 3 * NB;    // the ending radiance's first slot
   __shared__ wt sh_f[LDSF ? 6 * NB : 1];
   // Non-BVH kernels: the first round of the item's stream key (rt_rng.h), its pixel term and the
@@ -2344,6 +2358,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     // being held in SGPRs across the path loop (kparams())
     const kparams_t Q = kparams();
     L = xs_resolve(L, (uint32_t)depth >> 24);
+    if constexpr (ZCUT && (COUNT || DEFER)) {
+      // S9: a counting lane ran on for the counts only; a deferring lane found its zero after the
+      // next query and may have ended on that very bounce (0 * a non-finite background)
+      if (depth & kDead) L = mk(0., 0., 0.);
+    }
     double a0 = sh_acc[tid] + L.x, a1 = sh_acc[NB + tid] + L.y, a2 = sh_acc[2 * NB + tid] + L.z;
     alive = false;
     const int s_n = (int)(sij & 0xffffu) + 1;
@@ -2370,6 +2389,14 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         o[0] = a0, o[1] = a1, o[2] = a2;
       }
     }
+  };
+  // S9's condition on a lane in flight: throughput exactly 0 in all channels (an f32 product that
+  // underflowed included: it gathers 0 as well), no special value pending, not reference semantics.
+  // The flag is read through the kernarg pointer where it is used (kparams()): held in an SGPR
+  // across the loop it cost the BVH kernels, which spill SGPRs, 1.2 % (C4).
+  auto zero_beta = [&]() {
+    return ((kparams()->flags & RT_FLAG_SEMANTICS_REFERENCE) == 0u) & ((depth & kXsMask) == 0) &
+           ((beta.x == (wt)0) & (beta.y == (wt)0) & (beta.z == (wt)0));
   };
 
   for (;;) {
@@ -2607,6 +2634,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         }
 #endif
         beta = beta * factor;
+        // S9 where a kernel with the factor at the bounce itself cuts the lane: dead from here
+        // on, whatever this bounce turns out to be; the commit below ends the sample
+        if constexpr (ZCUT) {
+          if (zero_beta()) depth |= kDead;
+        }
       }
     } else {
       hit_w = Trav::template world<COUNT, VOL, BVH, VOLB, VOLI>(P, ro, rd, tm, t, hn, hf, g, C);
@@ -2885,7 +2917,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         PROF(6);
         factor = atten * (s_pdf * rcp_wt(pdf_val));
 #ifndef RT_ABL_NOXS  // ablation build: no special-value tracking (cost of RT_XS_*)
-        if (!(pdf_val != (wt)0)) {  // pdf_val 0 or NaN: the sample becomes inf / NaN (RT_XS_ON)
+        // pdf_val 0 or NaN: the sample becomes inf / NaN (RT_XS_ON); not on a lane that is already
+        // dead (a deferring lane on its last bounce: its sample ended with 0 a bounce ago, S9)
+        if (!(pdf_val != (wt)0) && !(ZCUT && DEFER && (depth & kDead))) {
           depth |= (int)((RT_XS_ON | xs_nan_bits(atten * s_pdf, beta)) << 24);
           beta = mkw(1, 1, 1);
           factor = beta;
@@ -2921,6 +2955,13 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const bool cut = !term && (depth & 0xffffff) == 0;
       C.inc_if(RT_OP_DEPTH_CUTOFF, cut);
       term |= cut;
+      // S9: a lane that goes on with zero throughput ends here with radiance 0, as a depth cutoff
+      // does (no set_le, no product with the background). kLpPend is not looked at: the lane may
+      // have parked a new factor in this iteration. The counting build only marks the lane.
+      if constexpr (ZCUT) {
+        if (!term && zero_beta()) depth |= kDead;
+        if constexpr (!COUNT) term |= (depth & kDead) != 0;
+      }
     }
     if (term & alive) {
       if constexpr (LDSF) {

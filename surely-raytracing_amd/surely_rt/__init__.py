@@ -33,6 +33,10 @@ RT_ERR_NO_DEVICE = -6
 
 RT_FLAG_OVERWRITE = 0x1
 RT_FLAG_COUNT_OPS = 0x2
+# exact reference semantics: empty lights -> error, Isotropic scattering_pdf = 0 (S1 / S2).
+# S9: a path whose throughput is exactly zero in all channels and that carries no special value
+# ends with radiance 0; the reference goes on and returns NaN if a later bounce has a zero or NaN
+# pdf; RT_FLAG_SEMANTICS_REFERENCE keeps the reference's behaviour.
 RT_FLAG_SEMANTICS_REFERENCE = 0x4
 RT_FLAG_INTERPRETER = 0x8  # product render with the interpreter walker (no scene-specialised kernel)
 RT_FLAG_REFERENCE_BVH = 0x10  # product render walks BVH subtrees in the reference tree and order
