@@ -4,6 +4,7 @@
 #   build/rt_render_cli    main.rs-equivalent host program (preset -> PPM)
 #   build/librtgather.so   RCCL framebuffer gather for one process per GPU (include/rt_gather.h)
 #   build/rng_key_check    host check of the split stream key (rt_rng.h)
+#   build/variant_check    host print-out of the path-kernel variant choice (rt_variant.h)
 #   build/librtprobe.so    one C function per device primitive and scene function (test infrastructure only)
 #   oracle/_build/*.so     CPU restatement (test infrastructure only)
 PKG      := surely-raytracing_amd
@@ -18,7 +19,7 @@ CFLAGS_O := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unuse
 
 HOST_SRC := $(CSRC)/host/scene.cpp $(CSRC)/host/presets.cpp $(CSRC)/host/capi.cpp
 DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
-DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
+DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
 .PHONY: all device host oracle cli gather checks probe clean
@@ -28,7 +29,7 @@ device: $(BUILD)/librtmi355x.so
 host: $(BUILD)/librthost.so
 cli: $(BUILD)/rt_render_cli
 gather: $(BUILD)/librtgather.so
-checks: $(BUILD)/rng_key_check
+checks: $(BUILD)/rng_key_check $(BUILD)/variant_check
 probe: $(BUILD)/librtprobe.so
 oracle: oracle/_build/liboracle_f32.so oracle/_build/liboracle_f64.so oracle/_build/liboracle_f64fma.so
 
@@ -85,10 +86,16 @@ $(BUILD)/rng_key_check: $(CSRC)/host/rng_key_check.cpp $(CSRC)/rt_rng.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall $< -o $@
 
+# the variant choice over every input, with the host compiler alone: rt_variant.h is plain C++
+# (tests/test_variant_choice.py runs it)
+$(BUILD)/variant_check: $(CSRC)/host/variant_check.cpp $(CSRC)/rt_variant.h $(CSRC)/rt_layout.h include/rt_mi355x.h
+	@mkdir -p $(BUILD)
+	g++ $(CXXFLAGS) -Iinclude $< -o $@
+
 # the device primitives of rt_kernel.h / rt_rng.h behind a C ABI, one by one, and the scene-level
 # functions on a flattened scene (tests/probe_lib.py): the product's HIPFLAGS, so each computes the
 # bits it computes in the path kernel, and the product's flattener; nothing links it
-$(BUILD)/librtprobe.so: $(CSRC)/probe/rt_probe.hip $(CSRC)/probe/rt_probe_scene.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(JIT_HDR) $(CSRC)/rt_flatten.hpp
+$(BUILD)/librtprobe.so: $(CSRC)/probe/rt_probe.hip $(CSRC)/probe/rt_probe_scene.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(JIT_HDR) $(CSRC)/rt_flatten.hpp $(CSRC)/rt_variant.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -shared $(filter %.hip %.cpp,$^) -o $@
 

@@ -35,6 +35,7 @@
 
 #include "../rt_kernel.h"
 #include "../rt_flatten.hpp"
+#include "../rt_variant.h"
 
 #define RTP_ERR_ARG (-100)
 #define RTP_ERR_BVH (-101)
@@ -216,18 +217,13 @@ __global__ void __launch_bounds__(kSceneBlock) scene_kernel(TraceParams P,
 }
 
 // The BVH entries' kernel: the BVH kernels' block size, and their prologue's copy of the compact
-// trees into LDS (rt_kernel.h trace_body) before any lane walks
+// trees into LDS (rt_kernel.h stage_lds; scene_upload stages nothing else) before any lane walks
 template <class K>
 __global__ void __launch_bounds__(kBlockBvh) scene_kernel_bvh(TraceParams P,
                                                               const double* __restrict__ in,
                                                               double* __restrict__ out, int n,
                                                               uint32_t arg) {
-  if (P.cbvh_lds_off != ~0u) {
-    const uint4* csrc = reinterpret_cast<const uint4*>(P.cbvh_src);
-    uint4* cdst = reinterpret_cast<uint4*>(rt_lds + P.cbvh_lds_off);
-    for (uint32_t k = threadIdx.x; k < P.cbvh_bytes / 16; k += blockDim.x) cdst[k] = csrc[k];
-  }
-  __syncthreads();
+  stage_lds<true, true>(P);
   const int i = (int)(blockIdx.x * (unsigned)kBlockBvh + threadIdx.x);
   if (i >= n) return;
   K::apply(P, in + (size_t)i * K::IN, out + (size_t)i * K::OUT, arg);
@@ -497,20 +493,16 @@ RTP_API int rtp_world_hit(const rt_scene_blob* blob, const double* in, double* o
   return scene_run<K_world_hit_t<false>>(blob, in, out, n, 0u, no_check);
 }
 
-// The kernel variant rt_device.hip / rtj::product_flags choose for the scene: VOL with a
-// ConstantMedium or an Isotropic material, VOLB unless every volume sits outside the BVH subtrees,
-// VOLI unless those are all one-walk spheres (the COUNT half keeps the interpreter).
+// The VOL, VOLB and VOLI of the product kernel's variant for the scene (rt_variant.h)
 RTP_API int rtp_world_hit_bvh(const rt_scene_blob* blob, const double* in, double* out, int n) {
   DevScene S;
   const int rc = scene_flatten(blob, S, true);
   if (rc) return rc;
-  const rtl_scene_header& H = S.F.hdr;
-  if (!H.has_bvh) return RTP_ERR_RECORD;
-  const bool vol = (H.has_volume | H.has_isotropic) != 0;
-  const bool novolb = vol && !H.volume_in_bvh;
-  if (!vol) return scene_run<K_world_hit_bvh_t<false, false, true>, true>(blob, in, out, n, 0u, no_check);
-  if (!novolb) return scene_run<K_world_hit_bvh_t<true, true, true>, true>(blob, in, out, n, 0u, no_check);
-  if (H.volumes_one_walk_spheres)
+  if (!S.F.hdr.has_bvh) return RTP_ERR_RECORD;
+  const rtv::Variant v = rtv::choose_variant(S.F.hdr, 0u, false);
+  if (!v.vol) return scene_run<K_world_hit_bvh_t<false, false, true>, true>(blob, in, out, n, 0u, no_check);
+  if (v.volb) return scene_run<K_world_hit_bvh_t<true, true, true>, true>(blob, in, out, n, 0u, no_check);
+  if (!v.voli)
     return scene_run<K_world_hit_bvh_t<true, false, false>, true>(blob, in, out, n, 0u, no_check);
   return scene_run<K_world_hit_bvh_t<true, false, true>, true>(blob, in, out, n, 0u, no_check);
 }

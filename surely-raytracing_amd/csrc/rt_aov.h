@@ -13,8 +13,8 @@
 //
 // The walker depends on the launch's LDS plan (rt_scene_impl.hpp plan_lds: staged tables, Perlin
 // tables, compact BVHs, the per-lane walk stacks at stack_lds_off) and on the workgroup size the
-// plan assumes (BlockOf<BVH>), so the staging prologue is trace_body's and the launch uses the
-// plan's block size; a workgroup holds blockDim / 64 tiles.
+// plan assumes (BlockOf<BVH>), so the prologue is the one trace_body runs (rt_kernel.h stage_lds
+// and make_tabs) and the launch uses the plan's block size; a workgroup holds blockDim / 64 tiles.
 #pragma once
 #include "rt_kernel.h"
 
@@ -24,45 +24,9 @@ template <bool VOL, bool TEX, bool BVH, bool STAGED, class Trav>
 __device__ __forceinline__ void aov_body(const TraceParams& P, float* __restrict__ aov) {
   constexpr bool COUNT = false;
   typedef typename cond<STAGED, lptr, gptr>::type TP;
-  // ---- LDS staging: trace_body's prologue (product build), region by region
-  if (P.stage_bytes || (BVH && !P.stage_scene && P.bvh_lds_words) ||
-      (BVH && P.cbvh_lds_off != ~0u)) {
-    const uint4* src = reinterpret_cast<const uint4*>(P.stage_src);
-    uint4* dst = reinterpret_cast<uint4*>(rt_lds);
-    const uint32_t n16 = P.stage_bytes / 16;
-    for (uint32_t k = threadIdx.x; k < n16; k += blockDim.x) dst[k] = src[k];
-    if (BVH && !P.stage_scene) {
-      const uint4* bsrc = reinterpret_cast<const uint4*>(P.nodes);
-      uint4* bdst = reinterpret_cast<uint4*>(rt_lds + P.bvh_lds_off);
-      const uint32_t b16 = P.bvh_lds_words / 4;
-      for (uint32_t k = threadIdx.x; k < b16; k += blockDim.x) bdst[k] = bsrc[k];
-    }
-    if (BVH && P.cbvh_lds_off != ~0u) {
-      const uint4* csrc = reinterpret_cast<const uint4*>(P.cbvh_src);
-      uint4* cdst = reinterpret_cast<uint4*>(rt_lds + P.cbvh_lds_off);
-      for (uint32_t k = threadIdx.x; k < P.cbvh_bytes / 16; k += blockDim.x) cdst[k] = csrc[k];
-    }
-    __syncthreads();
-  }
+  stage_lds<BVH, BVH>(P);  // the product build's prologue: no COUNT here
   TabsT<TP> T;
-  if constexpr (STAGED) {
-    typedef const __attribute__((address_space(3))) uint8_t* lbptr;
-    const lbptr b = (lbptr)rt_lds;
-    T.nodes = reinterpret_cast<lptr>(b);
-    T.mats = reinterpret_cast<lptr>(b + P.o_mats);
-    T.texs = reinterpret_cast<lptr>(b + P.o_texs);
-    T.lights = reinterpret_cast<lptr>(b + P.o_lights);
-    T.loffs = reinterpret_cast<lptr>(b + P.o_loffs);
-    T.perlin = rt_lds + P.o_perl;
-  } else {
-    const uint8_t* b = (const uint8_t*)P.nodes;
-    T.nodes = reinterpret_cast<gptr>(b);
-    T.mats = reinterpret_cast<gptr>(b + P.o_mats);
-    T.texs = reinterpret_cast<gptr>(b + P.o_texs);
-    T.lights = reinterpret_cast<gptr>(b + P.o_lights);
-    T.loffs = reinterpret_cast<gptr>(b + P.o_loffs);
-    T.perlin = rt_lds + (P.stage_scene ? P.o_perl : 0u);
-  }
+  make_tabs<STAGED>(P, T);
   Ctr<COUNT> C;
 
   // ---- tile and pixel of this lane (rt_reduce's mapping). A wave past the last tile leaves (no

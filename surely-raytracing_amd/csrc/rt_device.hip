@@ -39,27 +39,35 @@
 #include "rt_kernel.h"
 #include "rt_layout.h"
 #include "rt_scene_impl.hpp"
+#include "rt_variant.h"
 
 using namespace rtk;
 using namespace rts;
 
-namespace rts {
-// The tile-list variant (trace_body's TILES) of the ahead-of-time product kernel that
-// render_device_rows chose (rt_tiles.hip: a translation unit of its own, so the build compiles its
-// 18 instances beside this file's). set 0: [vol][tex][bvh]; 1: staged [vol][tex]; 2: BVH without
-// the walker's volume branch [no two-walk interpreter][tex]; 3: nested volumes [bvh].
-typedef void (*tile_kern_t)(TraceParams);
-RTS_HIDDEN tile_kern_t tile_trace_kernel(int set, int idx);
-}  // namespace rts
-
 namespace {
 
-// Ahead-of-time kernels: the interpreter traversal, one per feature combination.
-template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB = VOL,
-          bool VOLI = true, int VN = 0>
+// Ahead-of-time kernels: the interpreter traversal, one per row of RT_VARIANTS (rt_variant.h) and,
+// for the rows that keep the two-walk interpreter, one more that counts ops.
+template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, int VN>
 __global__ __launch_bounds__(BlockOf<BVH>::value, (MinWaves<VOL, TEX, BVH>::value)) void rt_trace(
     TraceParams P) {
   trace_body<COUNT, VOL, TEX, BVH, STAGED, VOLB, VOLI, TravInterpN<VN>>(P);
+}
+template <bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, int VN>
+constexpr kern_t count_kernel() {
+  if constexpr (VOLI)
+    return rt_trace<true, VOL, TEX, BVH, STAGED, VOLB, VOLI, VN>;
+  else
+    return nullptr;  // choose_variant keeps voli under RT_FLAG_COUNT_OPS
+}
+kern_t trace_kernel(const rtv::Variant& v, bool count) {
+#define RT_VARIANT_ROW(vol, tex, bvh, staged, volb, voli, vn)                    \
+  if (v == rtv::Variant{vol, tex, bvh, staged, volb, voli, vn})                  \
+    return count ? count_kernel<vol, tex, bvh, staged, volb, voli, vn>()         \
+                 : rt_trace<false, vol, tex, bvh, staged, volb, voli, vn>;
+  RT_VARIANTS(RT_VARIANT_ROW)
+#undef RT_VARIANT_ROW
+  return nullptr;
 }
 
 // Per pixel, in the reference's sample order (s_j, then s_i: render.rs:185-189): for each
@@ -564,7 +572,9 @@ int rt_jit_check(const rt_scene_blob* blob, const char* arch, int* state, char* 
   if (!walker.empty()) {
     std::vector<char> code;
     std::string log;
-    rc = rtj::compile(rtj::kernel_source(walker, rtj::product_flags(F, true)), arch, &code, &log);
+    // the variant of a product render whose plan stages the scene's tables
+    const rtv::Variant v = rtv::choose_variant(F.hdr, 0u, true);
+    rc = rtj::compile(rtj::kernel_source(walker, v, false), arch, &code, &log);
     if (rc != 0) {
       *state = -2;
       out = log;
@@ -573,9 +583,7 @@ int rt_jit_check(const rt_scene_blob* blob, const char* arch, int* state, char* 
     // too, so that the code-object cache holds both; the returned source is the plain walker's
     const char* tv = std::getenv("RT_JIT_CHECK_TILES");
     if (rc == 0 && tv && std::strcmp(tv, "1") == 0) {
-      rtj::Flags tf = rtj::product_flags(F, true);
-      tf.tiles = true;
-      rc = rtj::compile(rtj::kernel_source(walker, tf), arch, &code, &log);
+      rc = rtj::compile(rtj::kernel_source(walker, v, true), arch, &code, &log);
       if (rc != 0) {
         *state = -2;
         out = log;
@@ -660,28 +668,11 @@ int rts::acquire_slot(rt_scene* sc, std::unique_lock<std::mutex>& lock, hipStrea
   }
 }
 
-// A tile-list render's list (rt_render_tiles_device), validated by the entry point: strictly
-// ascending indices of the call's tile grid. n_px: the pixels of the listed tiles.
-struct TileJob {
-  const uint32_t* tiles;
-  uint32_t n_list;
-  int sj_step;
-  uint64_t n_px;
-};
-
-// m2 != nullptr: a moments render (rt_render_moments_device), which also writes the second
-// moments of the row totals; every other step is the plain render's. tj != nullptr: a tile-list
-// render (rt_render_tiles_device): the launch's pairs run over the list's entries and the strided
-// stratum rows sj_begin + k * sj_step, through the TILES variants of the same kernels; LDS plan,
-// kernel choice, slot, chunking and stats are shared.
-static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
-                              float* accum, float* m2, const TileJob* tj, void* stream_v,
-                              rt_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (!sc || !cam || !opts || !accum) return set_err(RT_ERR_INVALID_ARG, "null argument");
+int rts::check_render_args(const rt_camera* cam, const rt_render_opts* opts, bool path_depth,
+                           int sj_step, int* sj0_out, int* n_sj_out) {
   const int W = cam->image_width, S = cam->sqrt_spp;
-  if (W <= 0 || cam->image_height <= 0 || S <= 0 || cam->max_depth < 0 ||
-      cam->max_depth > 0xffffff || opts->n_rows < 0 ||
+  if (W <= 0 || cam->image_height <= 0 || S <= 0 ||
+      (path_depth && (cam->max_depth < 0 || cam->max_depth > 0xffffff)) || opts->n_rows < 0 ||
       opts->row_step <= 0 || opts->row_begin < 0)
     return set_err(RT_ERR_INVALID_ARG, "bad camera or row range");
   if (opts->n_rows > 0 &&
@@ -696,26 +687,16 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   if (S > 32768) return set_err(RT_ERR_UNSUPPORTED, "spp > 2^30 (sqrt_spp > 32768)");
   const int sj0 = opts->sj_count > 0 ? opts->sj_begin : 0;
   const int n_sj = opts->sj_count > 0 ? opts->sj_count : S;
-  const int sj_step = tj ? tj->sj_step : 1;
   if (sj0 < 0 || (int64_t)sj0 + (int64_t)(n_sj - 1) * sj_step + 1 > S)
     return set_err(RT_ERR_INVALID_ARG, "bad stratum range");
-  if (sc->hdr.n_lights == 0 && (opts->flags & RT_FLAG_SEMANTICS_REFERENCE) && sc->hdr.pdf_materials)
-    return set_err(RT_ERR_EMPTY_LIGHTS,
-                   "empty light list with a diffuse/volume material: the reference panics "
-                   "(hittable.rs:115-129)");
-  std::unique_lock<std::mutex> lock(sc->mu);
-  hipStream_t stream = (hipStream_t)stream_v;
-  HIP_TRY(hipSetDevice(sc->device));
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  const size_t n_px = (size_t)opts->n_rows * W;
-  if (n_px == 0) return RT_OK;
-  SlotHold hold{sc, lock};
-  {
-    const int rc = acquire_slot(sc, lock, stream, &hold.sl);
-    if (rc != RT_OK) return rc;
-  }
-  RenderSlot* const sl = hold.sl;
-  TraceParams P;
+  *sj0_out = sj0;
+  *n_sj_out = n_sj;
+  return RT_OK;
+}
+
+void rts::fill_trace_params(TraceParams* Pp, const rt_scene* sc, const rt_camera* cam,
+                            const rt_render_opts* opts, const LdsPlan& LP) {
+  TraceParams& P = *Pp;
   std::memset(&P, 0, sizeof(P));
   P.nodes = sc->nodes;
   P.mats = sc->mats;
@@ -724,8 +705,6 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   P.lights = sc->lights;
   P.light_offs = sc->light_offs;
   P.texels = sc->texels;
-  P.ops = sl->ops;
-  P.queue = sl->queue;
   P.root = sc->hdr.root;
   P.n_lights = sc->hdr.n_lights;
   P.lights_is_list = sc->hdr.lights_is_list;
@@ -733,26 +712,10 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   P.inv_n_lights = sc->hdr.n_lights ? 1.0 / (double)sc->hdr.n_lights : 0.0;
   P.sphere_light0 = sc->sphere_light0;
   P.flags = opts->flags;
-  const bool count = (opts->flags & RT_FLAG_COUNT_OPS) != 0;
-#ifdef RT_PROF  // profiling build: the product kernels also fill the ops buffer (section cycles)
-  const bool ops_buf = true;
-#else
-  const bool ops_buf = count;
-#endif
-  // VOL kernels: ConstantMedium nodes or an Isotropic material (also usable outside one)
-  const bool vol = (sc->hdr.has_volume | sc->hdr.has_isotropic) != 0;
-  const bool tex = sc->hdr.has_textures != 0;
-  const bool bvh = sc->hdr.has_bvh != 0;
-  // product renders of a generated scene run its scene-specialised kernel (same template
-  // arguments and launch bounds as the ahead-of-time kernel, top-level walk unrolled; rt_jit.cpp)
-  const bool want_jit = !count && !(opts->flags & RT_FLAG_INTERPRETER) && sc->jit_state >= 0;
   // LDS: staged tables, then the compact ordered BVHs (rt_layout.h CBVH) with the walk's
   // per-lane stacks, or as much of the reference BVH region as fits (plan_lds); with the compact
   // trees in LDS the reference BVH region stays in global memory (only lanes flagged for the
   // reference-order re-walk read it)
-  const LdsPlan LP = plan_lds(sc->hdr, sc->o_perl, opts->flags, want_jit, sc->lds_module_max);
-  const int block = LP.block;
-  const size_t static_lds = LP.static_lds;
   P.stage_scene = LP.stage_scene;
   P.n_perlin_lds = LP.n_perlin_lds;
   P.stage_src = LP.stage_scene ? sc->dev : sc->perlin;
@@ -770,7 +733,6 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   P.o_lights = sc->o_lights;
   P.o_loffs = sc->o_loffs;
   P.o_perl = sc->o_perl;
-  const size_t lds_bytes = LP.lds_bytes;
   for (int k = 0; k < 3; ++k) {
     P.center[k] = cam->center[k];
     P.p00[k] = cam->pixel00_loc[k];
@@ -783,215 +745,224 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   }
   P.rs = cam->recip_sqrt_spp;
   P.defocus = cam->defocus_angle > 0.0;
-  P.W = W;
+  P.W = cam->image_width;
   P.n_rows = opts->n_rows;
   P.row_begin = opts->row_begin;
   P.row_step = opts->row_step;
-  P.sqrt_spp = S;
+  P.sqrt_spp = cam->sqrt_spp;
   P.max_depth = cam->max_depth;
   P.seed_lo = (uint32_t)opts->seed;
   P.seed_hi = (uint32_t)(opts->seed >> 32);
-  P.tiles_x = (W + kWaveTile - 1) / kWaveTile;
-  const int tiles_y = (opts->n_rows + kWaveTile - 1) / kWaveTile;
-  // the launch's tiles: the call's whole grid, or the entries of the list
-  const int n_tiles = tj ? (int)tj->n_list : P.tiles_x * tiles_y;
-  P.sj_step = sj_step;
-  P.n_blk = (S + kPoolSi - 1) / kPoolSi;
-  typedef void (*kern_t)(TraceParams);
-  // [count][vol][tex][bvh]; a scene without a BVH whose tables are staged in LDS runs the
-  // STAGED variant (LDS-typed table reads), BVH kernels read the tables from global memory
-  static const kern_t table[16] = {
-      rt_trace<false, false, false, false, false>, rt_trace<false, false, false, true, false>,
-      rt_trace<false, false, true, false, false>,  rt_trace<false, false, true, true, false>,
-      rt_trace<false, true, false, false, false>,  rt_trace<false, true, false, true, false>,
-      rt_trace<false, true, true, false, false>,   rt_trace<false, true, true, true, false>,
-      rt_trace<true, false, false, false, false>,  rt_trace<true, false, false, true, false>,
-      rt_trace<true, false, true, false, false>,   rt_trace<true, false, true, true, false>,
-      rt_trace<true, true, false, false, false>,   rt_trace<true, true, false, true, false>,
-      rt_trace<true, true, true, false, false>,    rt_trace<true, true, true, true, false>};
-  // [count][vol][tex], no BVH, staged
-  static const kern_t table_staged[8] = {
-      rt_trace<false, false, false, false, true>, rt_trace<false, false, true, false, true>,
-      rt_trace<false, true, false, false, true>,  rt_trace<false, true, true, false, true>,
-      rt_trace<true, false, false, false, true>,  rt_trace<true, false, true, false, true>,
-      rt_trace<true, true, false, false, true>,   rt_trace<true, true, true, false, true>};
-  const bool staged = !bvh && P.stage_scene && !sc->hdr.nested_volumes;
-  const int kidx = ((opts->flags & RT_FLAG_COUNT_OPS) ? 8 : 0) + (vol ? 4 : 0) + (tex ? 2 : 0) +
-                   (bvh ? 1 : 0) + (staged ? 16 : 0);
-  // BVH scenes whose volumes all sit outside BVH subtrees (final_scene) run the variant whose
-  // per-lane walker has no volume branch; when those volumes are all one-walk spheres, the
-  // top-level walker carries no two-walk interpreter either
-  static const kern_t table_bvh_novolb[8] = {
-      rt_trace<false, true, false, true, false, false>, rt_trace<false, true, true, true, false, false>,
-      rt_trace<true, true, false, true, false, false>,  rt_trace<true, true, true, true, false, false>,
-      rt_trace<false, true, false, true, false, false, false>,
-      rt_trace<false, true, true, true, false, false, false>,
-      rt_trace<true, true, false, true, false, false, false>,
-      rt_trace<true, true, true, true, false, false, false>};
-  const bool novolb = bvh && vol && !sc->hdr.volume_in_bvh;
-  // the op-counting build always walks twice, so only product kernels drop the interpreter
-  const bool novoli = novolb && sc->hdr.volumes_one_walk_spheres && !(opts->flags & RT_FLAG_COUNT_OPS);
-  const int vb = (novoli ? 4 : 0) + (kidx >= 8 ? 2 : 0) + (tex ? 1 : 0);
-  kern_t kern = staged ? table_staged[kidx / 2 - 8] : (novolb ? table_bvh_novolb[vb] : table[kidx]);
-  int kslot = novolb ? 32 + vb : kidx;
-  // the same choice among the tile-list variants (rt_tiles.hip; product kernels only)
-  int tset = staged ? 1 : (novolb ? 2 : 0);
-  int tidx = staged ? kidx / 2 - 8 : (novolb ? (novoli ? 2 : 0) + (tex ? 1 : 0) : kidx);
-  // ConstantMedium nested in volume boundaries (rt_flatten.cpp: at most RTL_VOLUME_NEST deep):
-  // the generic texture/volume kernels that walk them (no scene-specialised kernel)
-  static const kern_t table_nested[4] = {
-      rt_trace<false, true, true, false, false, true, true, RTL_VOLUME_NEST>,
-      rt_trace<false, true, true, true, false, true, true, RTL_VOLUME_NEST>,
-      rt_trace<true, true, true, false, false, true, true, RTL_VOLUME_NEST>,
-      rt_trace<true, true, true, true, false, true, true, RTL_VOLUME_NEST>};
-  if (sc->hdr.nested_volumes) {
-    const int ni = ((opts->flags & RT_FLAG_COUNT_OPS) ? 2 : 0) + (bvh ? 1 : 0);
-    kern = table_nested[ni];
-    kslot = 44 + ni;
-    tset = 3;
-    tidx = bvh ? 1 : 0;
-  }
-  if (tj) {
-    kern = tile_trace_kernel(tset, tidx);
-    if (!kern) return set_err(RT_ERR_INVALID_ARG, "no tile-list variant of this kernel");
-  }
-  hipFunction_t jfn = nullptr;
-  if (want_jit && lds_bytes + static_lds <= sc->lds_module_max) {
-    rtj::Kernel& jk = sc->jit_k[(tex ? 1 : 0) + (staged ? 2 : 0) + (tj ? 4 : 0)];
-    if (!jk.fn) {
-      std::string log;
-      rtj::Flags jf;
-      jf.vol = vol;
-      jf.tex = tex;
-      jf.bvh = bvh;
-      jf.staged = staged;
-      jf.volb = novolb ? false : vol;
-      jf.voli = !novoli;
-      jf.tiles = tj != nullptr;
-      if (rtj::get_kernel(sc->jit_walker, sc->device, jf, &jk, &log) != 0) {
-        sc->jit_state = -2;
-        sc->jit_msg = log;
-      } else {
-        // a dispatch the hardware cannot place aborts the whole queue (the CP's register or
-        // LDS check), so the code object's resources are checked against this launch first:
-        // workgroup size, VGPRs x waves per SIMD within the 512-entry file, LDS within the CU
-        const int waves_per_simd = (block / 64 + 3) / 4;
-        const int regs = (jk.regs + 7) & ~7;
-        char why[256];
-        std::snprintf(why, sizeof(why),
-                      "scene-specialised kernel%s: %d regs, max %d threads, %d B static LDS, "
-                      "%d B scratch/lane; launch %d threads, %zu B dynamic LDS",
-                      jk.cached ? " (code-object cache)" : "", jk.regs, jk.max_threads,
-                      jk.static_lds, jk.scratch, block, lds_bytes);
-        if (jk.max_threads < block || regs * waves_per_simd > 512 ||
-            (size_t)jk.static_lds + lds_bytes > sc->lds_module_max ||
-            (size_t)jk.static_lds > static_lds) {
-          sc->jit_state = -2;
-          sc->jit_msg = std::string("not launched: ") + why;
-          rtj::release_kernel(jk);
-          jk = rtj::Kernel{};
-        } else {
-          sc->jit_msg = why;
-        }
-      }
-    }
-    if (jk.fn) {
-      sc->jit_state = 1;
-      jfn = jk.fn;
-      kslot = 40 + (tex ? 1 : 0) + (staged ? 2 : 0);
-    }
-  }
-  if (tj) kslot += rt_scene::kKernelSlots / 2;  // the tile-list variants' occupancy entries
-  // (module kernels take their dynamic LDS size at launch)
-  if (!jfn && lds_bytes > (64u << 10))
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes));
-  if (sc->resident_blocks[kslot] == 0 || sc->resident_lds[kslot] != lds_bytes) {
+  P.tiles_x = (cam->image_width + kWaveTile - 1) / kWaveTile;
+  P.sj_step = 1;
+  P.n_blk = (cam->sqrt_spp + kPoolSi - 1) / kPoolSi;
+}
+
+int rts::resident_blocks(rt_scene* sc, const void* kernel, hipFunction_t module, int block,
+                         size_t lds_bytes, const char* what, int* out) {
+  const void* key = module ? (const void*)module : kernel;
+  auto it = std::find_if(sc->resident.begin(), sc->resident.end(),
+                         [&](const rt_scene::Resident& r) { return r.kernel == key; });
+  if (it == sc->resident.end() || it->lds != lds_bytes) {
     int nb = 0;
     const hipError_t oe =
-        jfn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, jfn, block, lds_bytes)
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, block, lds_bytes);
+        module ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, module, block, lds_bytes)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds_bytes);
     if (oe != hipSuccess || nb <= 0)
-      return set_err(RT_ERR_HIP, std::string("occupancy query: the path kernel does not fit a CU (") +
+      return set_err(RT_ERR_HIP, std::string("occupancy query: the ") + what +
+                                     " does not fit a CU (" +
                                      (oe != hipSuccess ? hipGetErrorString(oe) : "0 blocks") + ")");
-    sc->resident_blocks[kslot] = nb;
-    sc->resident_lds[kslot] = lds_bytes;
+    if (it == sc->resident.end()) it = sc->resident.insert(it, rt_scene::Resident{key, 0, 0});
+    it->lds = lds_bytes;
+    it->blocks = nb;
   }
-  const int64_t max_blocks = (int64_t)sc->resident_blocks[kslot] * std::max(1, sc->n_cu);
-  // Outputs (TraceParams::part): one f64 RGB value per (pixel, s_j) of the row pairs, one per
-  // (pixel, s_j, block) of the segment pairs and one per sample of the tail pairs.
-  //  * A launch of many pairs per resident wave (a whole frame on one GPU: C2 has 60) renders
-  //    row items, then a band of segment items about four pairs per resident wave long, then a
-  //    tail of single samples an eighth of a pair per wave long. When the row pools run out, the
-  //    lanes still finishing a row have up to sqrt_spp paths left (rows through glass take
-  //    several times the mean), and the band keeps the other lanes busy meanwhile; the tail
-  //    does the same for the segments' last ~kPoolSi / 2 samples. The workspace is then about
-  //    one value per (pixel, s_j): C2 0.59 GB instead of 2.1.
-  //  * Smaller launches (an N-way share, chunks) balance better without rows (C2 over 8 GPUs:
-  //    0.940 of ideal with segments, 0.894 with half the pairs as rows, profiles/
-  //    r03_scaling_probe_*.log): segment items, then a tail of one pair per resident wave.
-  //  * BVH kernels render rows when their plan fits the row totals beside the compact trees.
-  // RT_SEG_PAIRS (rows with that band) and RT_TAIL_PAIRS override the sizes (tests: the image
-  // does not depend on the split).
-  const int64_t res_waves = max_blocks * (block / 64);
-  const bool rows_ok = !bvh || LP.row_lds_off != ~0u;
-  const char* seg_env = std::getenv("RT_SEG_PAIRS");
-  const char* tail_env = std::getenv("RT_TAIL_PAIRS");
-  struct Split {
-    int64_t pairs, r, a, values;  // row pairs [0, r), segment pairs [r, a), tail [a, pairs)
-  };
-  auto split = [&](int cn) {
-    Split sp;
-    sp.pairs = (int64_t)n_tiles * cn;
-    const bool rows = rows_ok && (seg_env ? true : sp.pairs >= 24 * res_waves);
-    int64_t tail = rows ? std::max<int64_t>(1, res_waves / 8) : res_waves;
-    if (tail_env) tail = std::strtoll(tail_env, nullptr, 10);
-    const int64_t band = seg_env ? std::strtoll(seg_env, nullptr, 10) : 4 * res_waves;
-    const int64_t tb = std::min<int64_t>(sp.pairs, std::max<int64_t>(0, tail));
-    sp.a = sp.pairs - tb;
-    sp.r = rows ? std::max<int64_t>(0, sp.a - std::max<int64_t>(0, band)) : 0;
-    sp.values = sp.r + (sp.a - sp.r) * P.n_blk + tb * S;  // 64-value slots
-    return sp;
-  };
-  // the chunks' carries: one f64 RGB value per pixel of the call, or per pixel slot of the list
-  const size_t n_carry = tj ? (size_t)n_tiles * 64 : n_px;
-  const size_t tot_bytes = (n_carry * 3 * sizeof(double) + 255) & ~(size_t)255;
-  const size_t val_bytes = (size_t)64 * 3 * sizeof(double);  // one f64 RGB value per pixel
-  auto part_bytes = [&](int cn) { return (size_t)split(cn).values * val_bytes; };
+  *out = it->blocks;
+  return RT_OK;
+}
+
+int rts::complete_render(SlotHold& hold, hipStream_t stream, rt_stats* stats,
+                         const rt_stats& counts, bool read_ops,
+                         std::chrono::steady_clock::time_point t0) {
+  RenderSlot* const sl = hold.sl;
+  if (stats) HIP_TRY(hipEventRecord(sl->ev1, stream));
+  HIP_TRY(hipEventRecord(sl->done, stream));
+  sl->recorded = true;
+  sl->last_stream = stream;
+  hold.finished = true;
+  if (stats) {
+    hold.lock.unlock();  // the slot stays held: other renders of the scene go on meanwhile
+    HIP_TRY(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, sl->ev0, sl->ev1));
+    stats->ms_kernel = ms;
+    stats->samples = counts.samples;
+    stats->out_bytes = counts.out_bytes;
+    stats->launches = counts.launches;
+    if (read_ops) {
+      unsigned long long h[32];
+      HIP_TRY(hipMemcpy(h, sl->ops, sizeof(h), hipMemcpyDeviceToHost));
+      for (int k = 0; k < 32; ++k) stats->ops[k] = h[k];
+    }
+    stats->ms_total =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return RT_OK;
+}
+
+// A tile-list render's list (rt_render_tiles_device), validated by the entry point: strictly
+// ascending indices of the call's tile grid. n_px: the pixels of the listed tiles.
+struct TileJob {
+  const uint32_t* tiles;
+  uint32_t n_list;
+  int sj_step;
+  uint64_t n_px;
+};
+
+namespace {
+
+// The kernel of a render: the ahead-of-time instance of the scene's variant (rt_variant.h), and
+// for product renders of a generated scene its scene-specialised kernel (same template arguments
+// and launch bounds, top-level walk unrolled; rt_jit.cpp), compiled on the first such render.
+struct PathKernel {
+  kern_t kern = nullptr;
+  hipFunction_t jfn = nullptr;  // runs instead of kern when set
+};
+int select_kernel(rt_scene* sc, uint32_t flags, const LdsPlan& LP, bool tiles, bool want_jit,
+                  PathKernel* out) {
+  const rtv::Variant v = rtv::choose_variant(sc->hdr, flags, LP.stage_scene != 0);
+  out->kern = tiles ? tile_trace_kernel(v) : trace_kernel(v, (flags & RT_FLAG_COUNT_OPS) != 0);
+  if (!out->kern)
+    return set_err(RT_ERR_INVALID_ARG, tiles ? "no tile-list variant of this kernel"
+                                             : "no ahead-of-time kernel of this variant");
+  if (!want_jit || LP.lds_bytes + LP.static_lds > sc->lds_module_max) return RT_OK;
+  rtj::Kernel& jk = sc->jit_k[tiles ? 1 : 0];
+  if (!jk.fn) {
+    std::string log;
+    if (rtj::get_kernel(sc->jit_walker, sc->device, v, tiles, &jk, &log) != 0) {
+      sc->jit_state = -2;
+      sc->jit_msg = log;
+    } else {
+      // a dispatch the hardware cannot place aborts the whole queue (the CP's register or
+      // LDS check), so the code object's resources are checked against this launch first:
+      // workgroup size, VGPRs x waves per SIMD within the 512-entry file, LDS within the CU
+      const int waves_per_simd = (LP.block / 64 + 3) / 4;
+      const int regs = (jk.regs + 7) & ~7;
+      char why[256];
+      std::snprintf(why, sizeof(why),
+                    "scene-specialised kernel%s: %d regs, max %d threads, %d B static LDS, "
+                    "%d B scratch/lane; launch %d threads, %zu B dynamic LDS",
+                    jk.cached ? " (code-object cache)" : "", jk.regs, jk.max_threads,
+                    jk.static_lds, jk.scratch, LP.block, LP.lds_bytes);
+      if (jk.max_threads < LP.block || regs * waves_per_simd > 512 ||
+          (size_t)jk.static_lds + LP.lds_bytes > sc->lds_module_max ||
+          (size_t)jk.static_lds > LP.static_lds) {
+        sc->jit_state = -2;
+        sc->jit_msg = std::string("not launched: ") + why;
+        rtj::release_kernel(jk);
+        jk = rtj::Kernel{};
+      } else {
+        sc->jit_msg = why;
+      }
+    }
+  }
+  if (jk.fn) {
+    sc->jit_state = 1;
+    out->jfn = jk.fn;
+  }
+  return RT_OK;
+}
+
+// Outputs (TraceParams::part): one f64 RGB value per (pixel, s_j) of the row pairs, one per
+// (pixel, s_j, block) of the segment pairs and one per sample of the tail pairs.
+//  * A launch of many pairs per resident wave (a whole frame on one GPU: C2 has 60) renders
+//    row items, then a band of segment items about four pairs per resident wave long, then a
+//    tail of single samples an eighth of a pair per wave long. When the row pools run out, the
+//    lanes still finishing a row have up to sqrt_spp paths left (rows through glass take
+//    several times the mean), and the band keeps the other lanes busy meanwhile; the tail
+//    does the same for the segments' last ~kPoolSi / 2 samples. The workspace is then about
+//    one value per (pixel, s_j): C2 0.59 GB instead of 2.1.
+//  * Smaller launches (an N-way share, chunks) balance better without rows (C2 over 8 GPUs:
+//    0.940 of ideal with segments, 0.894 with half the pairs as rows, profiles/
+//    r03_scaling_probe_*.log): segment items, then a tail of one pair per resident wave.
+//  * BVH kernels render rows when their plan fits the row totals beside the compact trees.
+// RT_SEG_PAIRS (rows with that band) and RT_TAIL_PAIRS override the sizes (tests: the image
+// does not depend on the split).
+struct WorkIn {
+  int n_tiles, n_sj, S, n_blk;  // the launch's tiles, the call's stratum rows, sqrt_spp, its blocks
+  int64_t res_waves;            // waves the device holds at once
+  bool rows_ok;                 // the kernel renders row items
+  size_t n_carry;               // pixels (or pixel slots of the list) carried between chunks
+  size_t mem_total;             // device memory
+  const char *seg_pairs, *tail_pairs, *workspace_mb;  // RT_SEG_PAIRS, RT_TAIL_PAIRS, RT_WORKSPACE_MB
+};
+struct Split {
+  int64_t pairs, r, a, values;  // row pairs [0, r), segment pairs [r, a), tail [a, pairs)
+};
+Split split_pairs(const WorkIn& in, int cn) {
+  Split sp;
+  sp.pairs = (int64_t)in.n_tiles * cn;
+  const bool rows = in.rows_ok && (in.seg_pairs ? true : sp.pairs >= 24 * in.res_waves);
+  int64_t tail = rows ? std::max<int64_t>(1, in.res_waves / 8) : in.res_waves;
+  if (in.tail_pairs) tail = std::strtoll(in.tail_pairs, nullptr, 10);
+  const int64_t band = in.seg_pairs ? std::strtoll(in.seg_pairs, nullptr, 10) : 4 * in.res_waves;
+  const int64_t tb = std::min<int64_t>(sp.pairs, std::max<int64_t>(0, tail));
+  sp.a = sp.pairs - tb;
+  sp.r = rows ? std::max<int64_t>(0, sp.a - std::max<int64_t>(0, band)) : 0;
+  sp.values = sp.r + (sp.a - sp.r) * in.n_blk + tb * in.S;  // 64-value slots
+  return sp;
+}
+constexpr size_t kValBytes = (size_t)64 * 3 * sizeof(double);  // one f64 RGB value per pixel
+size_t part_bytes(const WorkIn& in, int cn) { return (size_t)split_pairs(in, cn).values * kValBytes; }
+// The workspace of a render: the chunks' carries (one f64 RGB value per pixel of the call, or per
+// pixel slot of the list), then the largest chunk's outputs. Chunks of stratum rows keep it under
+// RT_WORKSPACE_MB (default 40 GiB, at most a quarter of the device's memory): the whole C5 frame
+// (3840 x 2160, 10000 spp, ~19 GB of row totals) renders in one launch; 800x800 x 961 spp takes
+// one (~0.59 GB). A pure function of `in`.
+struct WorkPlan {
+  int chunk;          // stratum rows per launch
+  size_t tot_bytes;   // the carries
+  size_t need;        // the whole workspace
+  bool indexable;     // the chunk's outputs and pools fit their 32- and 31-bit indices
+};
+WorkPlan plan_workspace(const WorkIn& in) {
+  WorkPlan wp;
+  wp.tot_bytes = (in.n_carry * 3 * sizeof(double) + 255) & ~(size_t)255;
   // a launch's f64 RGB outputs are indexed in 32 bits (end_sample) and its pools in 31
   auto indexable = [&](int cn) {
-    const Split sp = split(cn);
-    return sp.values * 64 < (1ll << 32) && sp.r + (sp.pairs - sp.r) * P.n_blk <= 0x7fffffff;
+    const Split sp = split_pairs(in, cn);
+    return sp.values * 64 < (1ll << 32) && sp.r + (sp.pairs - sp.r) * in.n_blk <= 0x7fffffff;
   };
-  // Chunks of stratum rows keep the workspace under RT_WORKSPACE_MB (default 40 GiB, at most a
-  // quarter of the device's memory): the whole C5 frame (3840 x 2160, 10000 spp, ~19 GB of row
-  // totals) renders in one launch; 800x800 x 961 spp takes one (~0.59 GB).
-  size_t cap = std::min<size_t>((size_t)40960 << 20, sc->mem_total / 4);
-  if (const char* e = std::getenv("RT_WORKSPACE_MB")) cap = (size_t)std::strtoull(e, nullptr, 10) << 20;
-  int chunk = n_sj;
-  while (chunk > 1 && (tot_bytes + part_bytes(chunk) > cap || !indexable(chunk)))
-    chunk = (chunk + 1) / 2;
-  const size_t need = tot_bytes + part_bytes(chunk);
-  if (!indexable(chunk)) return set_err(RT_ERR_UNSUPPORTED, "grid too large");
-  if (need > sl->work_bytes) {
-    // the slot's previous render (another stream's, or this one's) may still read the old
-    // workspace: let it finish first
+  size_t cap = std::min<size_t>((size_t)40960 << 20, in.mem_total / 4);
+  if (in.workspace_mb) cap = (size_t)std::strtoull(in.workspace_mb, nullptr, 10) << 20;
+  wp.chunk = in.n_sj;
+  while (wp.chunk > 1 && (wp.tot_bytes + part_bytes(in, wp.chunk) > cap || !indexable(wp.chunk)))
+    wp.chunk = (wp.chunk + 1) / 2;
+  wp.need = wp.tot_bytes + part_bytes(in, wp.chunk);
+  wp.indexable = indexable(wp.chunk);
+  return wp;
+}
+
+// The slot's buffers for this render: the workspace, a moments render's second carry when it runs
+// in several chunks, a tile-list render's list. Each is touched only after the slot's previous
+// render (another stream's, or this one's) has finished with it.
+int grow_slot(RenderSlot* sl, const WorkPlan& wp, bool m2_chunked, const TileJob* tj) {
+  if (wp.need > sl->work_bytes) {
     if (sl->recorded) HIP_TRY(hipEventSynchronize(sl->done));
     if (sl->work) HIP_TRY(hipFree(sl->work));
     sl->work = nullptr;
     sl->work_bytes = 0;
-    HIP_TRY(hipMalloc(&sl->work, need));
-    sl->work_bytes = need;
+    HIP_TRY(hipMalloc(&sl->work, wp.need));
+    sl->work_bytes = wp.need;
   }
   // a moments render in several chunks carries its second moments in a buffer of the slot's own,
   // allocated by the first such render (plain renders never pay for it)
-  if (m2 && chunk < n_sj && tot_bytes > sl->work2_bytes) {
+  if (m2_chunked && wp.tot_bytes > sl->work2_bytes) {
     if (sl->recorded) HIP_TRY(hipEventSynchronize(sl->done));
     if (sl->work2) HIP_TRY(hipFree(sl->work2));
     sl->work2 = nullptr;
     sl->work2_bytes = 0;
-    HIP_TRY(hipMalloc(&sl->work2, tot_bytes));
-    sl->work2_bytes = tot_bytes;
+    HIP_TRY(hipMalloc(&sl->work2, wp.tot_bytes));
+    sl->work2_bytes = wp.tot_bytes;
   }
   if (tj) {
     // the list travels through the slot: a host copy (the caller may free its list on return) and
@@ -1008,11 +979,129 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
       sl->tiles_cap = tj->n_list;
     }
     sl->tiles_host.assign(tj->tiles, tj->tiles + tj->n_list);
-    P.tile_list = sl->tiles;
   }
-  double* tot = (double*)sl->work;
-  double* tot2 = (double*)sl->work2;  // read and written only between chunks
-  P.part = (double*)(sl->work + tot_bytes);
+  return RT_OK;
+}
+
+// One rt_reduce launch over (M2, TILES), with the instance's own MomentsOut / TileIn arguments,
+// of the chunk P describes; the carries live in the slot (tot2: only between chunks)
+template <bool M2, bool TILES>
+void launch_reduce(const TraceParams& P, RenderSlot* sl, float* accum, float* m2, int n_tiles,
+                   int mode, hipStream_t stream) {
+  MomentsOut<M2> mo;
+  if constexpr (M2) mo = {(double*)sl->work2, m2};
+  TileIn<TILES> ti;
+  if constexpr (TILES) ti = {sl->tiles};
+  hipLaunchKernelGGL((rt_reduce<M2, TILES>), dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0,
+                     stream, P.part, (double*)sl->work, accum, P.W, P.n_rows, P.tiles_x, n_tiles,
+                     P.n_sj, P.sqrt_spp, P.n_pairs_r, P.n_pairs_a, mode, mo, ti);
+}
+
+// The launches of a render: per chunk of stratum rows sj0 + (k0 .. k0 + cn - 1) * sj_step one path
+// kernel over the chunk's pools and one rt_reduce into the carries or, last, the accumulator.
+int launch_chunks(rt_scene* sc, RenderSlot* sl, const PathKernel& K, TraceParams& P,
+                  const LdsPlan& LP, const WorkIn& in, const WorkPlan& wp, int64_t max_blocks,
+                  int sj0, uint32_t flags, float* accum, float* m2, bool tiles,
+                  hipStream_t stream, rt_stats* counts) {
+  static void (*const reduce[2][2])(const TraceParams&, RenderSlot*, float*, float*, int, int,
+                                    hipStream_t) = {
+      {launch_reduce<false, false>, launch_reduce<false, true>},
+      {launch_reduce<true, false>, launch_reduce<true, true>}};
+  const int block = LP.block;
+  for (int k0 = 0; k0 < in.n_sj; k0 += wp.chunk) {
+    const int cn = std::min(wp.chunk, in.n_sj - k0);
+    counts->out_bytes += part_bytes(in, cn);
+    ++counts->launches;
+    const Split sp = split_pairs(in, cn);
+    P.sj0 = sj0 + k0 * P.sj_step;
+    P.n_sj = cn;
+    P.n_pairs_r = (int)sp.r;
+    P.n_pairs_a = (int)sp.a;
+    P.n_pools = (int)(sp.r + (sp.pairs - sp.r) * P.n_blk);
+    // persistent grid: as many waves as the device holds at once (never more than pools)
+    const int64_t blocks = std::min(max_blocks, ((int64_t)P.n_pools + (block / 64) - 1) / (block / 64));
+    HIP_TRY(hipMemsetAsync(sl->queue, 0, sizeof(unsigned int), stream));
+    const int ring = (int)(sc->n_tev % rt_scene::kTraceRing);
+    HIP_TRY(hipEventRecord(sc->tev[ring][0], stream));
+    if (K.jfn) {
+      void* args[] = {&P};
+      HIP_TRY(hipModuleLaunchKernel(K.jfn, (unsigned)blocks, 1, 1, (unsigned)block, 1, 1,
+                                    (unsigned)LP.lds_bytes, stream, args, nullptr));
+    } else {
+      hipLaunchKernelGGL(K.kern, dim3((unsigned)blocks), dim3(block), LP.lds_bytes, stream, P);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc->tev[ring][1], stream));
+    sc->tev_render[ring] = sc->n_render;
+    ++sc->n_tev;
+    const int mode =
+        (k0 == 0 ? 1 : 0) | (k0 + cn == in.n_sj ? 2 : 0) | ((flags & RT_FLAG_OVERWRITE) ? 4 : 0);
+    reduce[m2 != nullptr][tiles](P, sl, accum, m2, in.n_tiles, mode, stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+// m2 != nullptr: a moments render (rt_render_moments_device), which also writes the second
+// moments of the row totals; every other step is the plain render's. tj != nullptr: a tile-list
+// render (rt_render_tiles_device): the launch's pairs run over the list's entries and the strided
+// stratum rows sj_begin + k * sj_step, through the TILES variants of the same kernels; LDS plan,
+// kernel choice, slot, chunking and stats are shared.
+static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
+                              float* accum, float* m2, const TileJob* tj, void* stream_v,
+                              rt_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  int sj0 = 0, n_sj = 0;
+  RT_TRY(check_render_args(cam, opts, true, tj ? tj->sj_step : 1, &sj0, &n_sj));
+  if (sc->hdr.n_lights == 0 && (opts->flags & RT_FLAG_SEMANTICS_REFERENCE) && sc->hdr.pdf_materials)
+    return set_err(RT_ERR_EMPTY_LIGHTS,
+                   "empty light list with a diffuse/volume material: the reference panics "
+                   "(hittable.rs:115-129)");
+  std::unique_lock<std::mutex> lock(sc->mu);
+  hipStream_t stream = (hipStream_t)stream_v;
+  HIP_TRY(hipSetDevice(sc->device));
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const size_t n_px = (size_t)opts->n_rows * cam->image_width;
+  if (n_px == 0) return RT_OK;
+  SlotHold hold{sc, lock};
+  RT_TRY(acquire_slot(sc, lock, stream, &hold.sl));
+  RenderSlot* const sl = hold.sl;
+  const bool count = (opts->flags & RT_FLAG_COUNT_OPS) != 0;
+#ifdef RT_PROF  // profiling build: the product kernels also fill the ops buffer (section cycles)
+  const bool ops_buf = true;
+#else
+  const bool ops_buf = count;
+#endif
+  const bool want_jit = !count && !(opts->flags & RT_FLAG_INTERPRETER) && sc->jit_state >= 0;
+  const LdsPlan LP = plan_lds(sc->hdr, sc->o_perl, opts->flags, want_jit, sc->lds_module_max);
+  TraceParams P;
+  fill_trace_params(&P, sc, cam, opts, LP);
+  P.ops = sl->ops;
+  P.queue = sl->queue;
+  if (tj) P.sj_step = tj->sj_step;
+  PathKernel K;
+  RT_TRY(select_kernel(sc, opts->flags, LP, tj != nullptr, want_jit, &K));
+  // (module kernels take their dynamic LDS size at launch)
+  if (!K.jfn && LP.lds_bytes > (64u << 10))
+    HIP_TRY(hipFuncSetAttribute((const void*)K.kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)LP.lds_bytes));
+  int resident = 0;
+  RT_TRY(resident_blocks(sc, (const void*)K.kern, K.jfn, LP.block, LP.lds_bytes, "path kernel",
+                         &resident));
+  const int64_t max_blocks = (int64_t)resident * std::max(1, sc->n_cu);
+  // the launch's tiles: the call's whole grid, or the entries of the list
+  const int n_tiles = tj ? (int)tj->n_list : P.tiles_x * ((opts->n_rows + kWaveTile - 1) / kWaveTile);
+  const WorkIn in{n_tiles, n_sj, cam->sqrt_spp, P.n_blk, max_blocks * (LP.block / 64),
+                  !sc->hdr.has_bvh || LP.row_lds_off != ~0u, tj ? (size_t)n_tiles * 64 : n_px,
+                  sc->mem_total, std::getenv("RT_SEG_PAIRS"), std::getenv("RT_TAIL_PAIRS"),
+                  std::getenv("RT_WORKSPACE_MB")};
+  const WorkPlan wp = plan_workspace(in);
+  if (!wp.indexable) return set_err(RT_ERR_UNSUPPORTED, "grid too large");
+  RT_TRY(grow_slot(sl, wp, m2 && wp.chunk < n_sj, tj));
+  if (tj) P.tile_list = sl->tiles;
+  P.part = (double*)(sl->work + wp.tot_bytes);
   hold.stream = stream;
   hold.enqueued = true;  // from here on a failure still records `done` (SlotHold)
   if (ops_buf) HIP_TRY(hipMemsetAsync(sl->ops, 0, sizeof(unsigned long long) * 32, stream));
@@ -1025,80 +1114,12 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   HIP_TRY(hipMemsetAsync(sl->ops + 40, 0, sizeof(unsigned long long) * 21, stream));
 #endif
   if (stats) HIP_TRY(hipEventRecord(sl->ev0, stream));
-  uint64_t out_bytes = 0;
-  uint32_t launches = 0;
-  // chunk k0 renders the call's stratum rows sj0 + (k0 .. k0 + cn - 1) * sj_step
-  for (int k0 = 0; k0 < n_sj; k0 += chunk) {
-    const int cn = std::min(chunk, n_sj - k0);
-    out_bytes += part_bytes(cn);
-    ++launches;
-    const Split sp = split(cn);
-    P.sj0 = sj0 + k0 * sj_step;
-    P.n_sj = cn;
-    P.n_pairs_r = (int)sp.r;
-    P.n_pairs_a = (int)sp.a;
-    P.n_pools = (int)(sp.r + (sp.pairs - sp.r) * P.n_blk);
-    // persistent grid: as many waves as the device holds at once (never more than pools)
-    const int64_t blocks = std::min(max_blocks, ((int64_t)P.n_pools + (block / 64) - 1) / (block / 64));
-    HIP_TRY(hipMemsetAsync(sl->queue, 0, sizeof(unsigned int), stream));
-    const int ring = (int)(sc->n_tev % rt_scene::kTraceRing);
-    HIP_TRY(hipEventRecord(sc->tev[ring][0], stream));
-    if (jfn) {
-      void* args[] = {&P};
-      HIP_TRY(hipModuleLaunchKernel(jfn, (unsigned)blocks, 1, 1, (unsigned)block, 1, 1,
-                                    (unsigned)lds_bytes, stream, args, nullptr));
-    } else {
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(block), lds_bytes, stream, P);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc->tev[ring][1], stream));
-    sc->tev_render[ring] = sc->n_render;
-    ++sc->n_tev;
-    const int mode = (k0 == 0 ? 1 : 0) | (k0 + cn == n_sj ? 2 : 0) |
-                     ((opts->flags & RT_FLAG_OVERWRITE) ? 4 : 0);
-    const dim3 rgrid((unsigned)((n_tiles + 3) / 4));
-    if (tj && m2)
-      hipLaunchKernelGGL((rt_reduce<true, true>), rgrid, dim3(256), 0, stream, P.part, tot, accum,
-                         W, opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<true>{tot2, m2}, TileIn<true>{sl->tiles});
-    else if (tj)
-      hipLaunchKernelGGL((rt_reduce<false, true>), rgrid, dim3(256), 0, stream, P.part, tot, accum,
-                         W, opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<false>{}, TileIn<true>{sl->tiles});
-    else if (m2)
-      hipLaunchKernelGGL(rt_reduce<true>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
-                         opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<true>{tot2, m2}, TileIn<false>{});
-    else
-      hipLaunchKernelGGL(rt_reduce<false>, rgrid, dim3(256), 0, stream, P.part, tot, accum, W,
-                         opts->n_rows, P.tiles_x, n_tiles, cn, S, P.n_pairs_r, P.n_pairs_a, mode,
-                         MomentsOut<false>{}, TileIn<false>{});
-    HIP_TRY(hipGetLastError());
-  }
+  rt_stats counts{};
+  counts.samples = (uint64_t)(tj ? tj->n_px : n_px) * (uint64_t)n_sj * (uint64_t)cam->sqrt_spp;
+  RT_TRY(launch_chunks(sc, sl, K, P, LP, in, wp, max_blocks, sj0, opts->flags, accum, m2,
+                       tj != nullptr, stream, &counts));
   ++sc->n_render;
-  if (stats) HIP_TRY(hipEventRecord(sl->ev1, stream));
-  HIP_TRY(hipEventRecord(sl->done, stream));
-  sl->recorded = true;
-  sl->last_stream = stream;
-  hold.finished = true;
-  if (stats) {
-    lock.unlock();  // the slot stays held: other renders of the scene go on meanwhile
-    HIP_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, sl->ev0, sl->ev1));
-    stats->ms_kernel = ms;
-    stats->samples = (uint64_t)(tj ? tj->n_px : n_px) * (uint64_t)n_sj * (uint64_t)S;
-    stats->out_bytes = out_bytes;
-    stats->launches = launches;
-    if (ops_buf) {
-      unsigned long long h[32];
-      HIP_TRY(hipMemcpy(h, sl->ops, sizeof(h), hipMemcpyDeviceToHost));
-      for (int k = 0; k < 32; ++k) stats->ops[k] = h[k];
-    }
-    stats->ms_total =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return RT_OK;
+  return complete_render(hold, stream, stats, counts, ops_buf, t0);
 }
 
 // rt_render_device and rt_render_moments_device (m2 != nullptr): tall row ranges as sub-calls

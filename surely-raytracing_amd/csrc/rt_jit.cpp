@@ -688,22 +688,7 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
   return generate_walker(F, nullptr, why);
 }
 
-Flags product_flags(const rtf::FlatScene& F, bool staged) {
-  Flags f;
-  f.vol = (F.hdr.has_volume | F.hdr.has_isotropic) != 0;
-  f.tex = F.hdr.has_textures != 0;
-  f.bvh = F.hdr.has_bvh != 0;
-  f.staged = staged && !f.bvh;
-  // rt_device.hip: BVH scenes whose volumes all sit outside BVH subtrees run the per-lane walker
-  // without its volume branch, and without the two-walk interpreter when every boundary is a
-  // one-walk sphere
-  const bool novolb = f.bvh && f.vol && !F.hdr.volume_in_bvh;
-  f.volb = novolb ? false : f.vol;
-  f.voli = !(novolb && F.hdr.volumes_one_walk_spheres);
-  return f;
-}
-
-std::string kernel_source(const std::string& walker, const Flags& f) {
+std::string kernel_source(const std::string& walker, const rtv::Variant& f, bool tiles) {
   auto b = [](bool v) { return v ? "true" : "false"; };
   std::ostringstream src;
   src << "#include \"rt_kernel.h\"\nnamespace rtk {\n"
@@ -716,7 +701,7 @@ std::string kernel_source(const std::string& walker, const Flags& f) {
       << b(f.staged) << ", " << b(f.volb) << ", " << b(f.voli) << ", TravGen"
       // the plain kernel's text stays as it was: the flag is part of the source (and so of the
       // module cache's and the code-object cache's keys) only when set
-      << (f.tiles ? ", true" : "") << ">(P);\n}\n";
+      << (tiles ? ", true" : "") << ">(P);\n}\n";
   return src.str();
 }
 
@@ -953,9 +938,9 @@ void release_kernel(const Kernel& k) {
   evict_idle_locked();
 }
 
-int get_kernel(const std::string& walker, int device, const Flags& f, Kernel* out,
-               std::string* log) {
-  const std::string s = kernel_source(walker, f);
+int get_kernel(const std::string& walker, int device, const rtv::Variant& v, bool tiles,
+               Kernel* out, std::string* log) {
+  const std::string s = kernel_source(walker, v, tiles);
   std::lock_guard<std::mutex> lock(g_mu);
   // compile() reads RT_JIT_SRC_DIR's headers and RT_JIT_OPTS's options when set (diagnostics):
   // part of the module's identity, so an A/B in one process gets one module per setting

@@ -2181,25 +2181,13 @@ struct TravInterpN {
 };
 typedef TravInterpN<0> TravInterp;
 
-// The path kernel body; instantiated by rt_device.hip (interpreter) and by scene-specialised
-// JIT kernels. Its __global__ wrapper passes TraceParams as the only kernel argument (kparams()).
-// TILES: the launch's pairs are compact over a host-validated list of tiles and a strided set of
-// stratum rows (TraceParams::tile_list, sj_step); only the pixel coordinates and the stratum row of
-// the RNG key and jitter come from them, every pair, slot and pool index stays the position in the list.
-template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, class Trav,
-          bool TILES = false>
-__device__ __forceinline__ void trace_body(const TraceParams& P) {
-  // STAGED: the small-table prefix is in LDS (P.stage_scene) and per-lane table reads are
-  // ds_reads through 32-bit LDS pointers; otherwise they read the global tables.
-  typedef typename cond<STAGED, lptr, gptr>::type TP;
-  __shared__ unsigned int sh_ops[COUNT ? RT_OP_COUNT : 1];
-  if (COUNT) {
-    for (int k = threadIdx.x; k < RT_OP_COUNT; k += blockDim.x) sh_ops[k] = 0u;
-    __syncthreads();
-  }
+// The prologue of every kernel that walks a scene on the launch's LDS plan (rt_scene_impl.hpp
+// plan_lds): the whole workgroup copies the small tables (or just the Perlin tables) into LDS, then
+// the reference BVH region, then (CBVH) the compact trees, and meets at a barrier.
+template <bool BVH, bool CBVH>
+__device__ __forceinline__ void stage_lds(const TraceParams& P) {
   if (P.stage_bytes || (BVH && !P.stage_scene && P.bvh_lds_words) ||
-      (BVH && !COUNT && P.cbvh_lds_off != ~0u)) {
-    // copy the small tables (or just the Perlin tables) into LDS, then the BVH region
+      (CBVH && P.cbvh_lds_off != ~0u)) {
     const uint4* src = reinterpret_cast<const uint4*>(P.stage_src);
     uint4* dst = reinterpret_cast<uint4*>(rt_lds);
     const uint32_t n16 = P.stage_bytes / 16;
@@ -2210,14 +2198,19 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const uint32_t b16 = P.bvh_lds_words / 4;
       for (uint32_t k = threadIdx.x; k < b16; k += blockDim.x) bdst[k] = bsrc[k];
     }
-    if (BVH && !COUNT && P.cbvh_lds_off != ~0u) {
+    if (CBVH && P.cbvh_lds_off != ~0u) {
       const uint4* csrc = reinterpret_cast<const uint4*>(P.cbvh_src);
       uint4* cdst = reinterpret_cast<uint4*>(rt_lds + P.cbvh_lds_off);
       for (uint32_t k = threadIdx.x; k < P.cbvh_bytes / 16; k += blockDim.x) cdst[k] = csrc[k];
     }
     __syncthreads();
   }
-  TabsT<TP> T;
+}
+// The scene's tables as the kernel reads them: STAGED from the LDS copy of the small-table prefix
+// (P.stage_scene) through 32-bit LDS pointers, otherwise from global memory.
+template <bool STAGED>
+__device__ __forceinline__ void make_tabs(const TraceParams& P,
+                                          TabsT<typename cond<STAGED, lptr, gptr>::type>& T) {
   if constexpr (STAGED) {
     typedef const __attribute__((address_space(3))) uint8_t* lbptr;
     const lbptr b = (lbptr)rt_lds;
@@ -2236,6 +2229,27 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     T.loffs = reinterpret_cast<gptr>(b + P.o_loffs);
     T.perlin = rt_lds + (P.stage_scene ? P.o_perl : 0u);
   }
+}
+
+// The path kernel body; instantiated by rt_device.hip (interpreter) and by scene-specialised
+// JIT kernels. Its __global__ wrapper passes TraceParams as the only kernel argument (kparams()).
+// TILES: the launch's pairs are compact over a host-validated list of tiles and a strided set of
+// stratum rows (TraceParams::tile_list, sj_step); only the pixel coordinates and the stratum row of
+// the RNG key and jitter come from them, every pair, slot and pool index stays the position in the list.
+template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, class Trav,
+          bool TILES = false>
+__device__ __forceinline__ void trace_body(const TraceParams& P) {
+  // STAGED: the small-table prefix is in LDS (P.stage_scene) and per-lane table reads are
+  // ds_reads through 32-bit LDS pointers; otherwise they read the global tables.
+  typedef typename cond<STAGED, lptr, gptr>::type TP;
+  __shared__ unsigned int sh_ops[COUNT ? RT_OP_COUNT : 1];
+  if (COUNT) {
+    for (int k = threadIdx.x; k < RT_OP_COUNT; k += blockDim.x) sh_ops[k] = 0u;
+    __syncthreads();
+  }
+  stage_lds<BVH, BVH && !COUNT>(P);  // the op-counting build walks the reference trees only
+  TabsT<TP> T;
+  make_tabs<STAGED>(P, T);
   Ctr<COUNT> C;
 #ifdef RT_PROF
   if (threadIdx.x < 16) prof_trav[threadIdx.x] = 0ull;

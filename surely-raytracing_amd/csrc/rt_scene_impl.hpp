@@ -1,10 +1,12 @@
 // rt_scene_impl.hpp — the host-side scene and render-slot types shared by the translation units of
-// librtmi355x.so that launch kernels on a scene: rt_device.hip (the path kernels and the C ABI's
-// scene functions, where everything declared here is defined) and rt_aov.hip (the first-hit AOV
-// pass). Internal: nothing here is part of the C ABI.
+// librtmi355x.so that launch kernels on a scene, and the steps every such launch takes (argument
+// checks, LDS plan, TraceParams fill, occupancy query, completion): rt_device.hip (the path kernels
+// and the C ABI's scene functions, where everything declared here is defined) and rt_aov.hip (the
+// first-hit AOV pass). Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -17,6 +19,10 @@
 
 #define RTS_HIDDEN __attribute__((visibility("hidden")))
 
+namespace rtk {
+struct TraceParams;  // rt_kernel.h
+}
+
 namespace rts {
 
 // status code + the thread's rt_last_error() message
@@ -27,6 +33,13 @@ RTS_HIDDEN int set_err(int code, const std::string& m);
     hipError_t e_ = (expr);                                                                  \
     if (e_ != hipSuccess)                                                                    \
       return rts::set_err(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
+  } while (0)
+
+// a step of a call that returns an rt status: leave with it unless RT_OK
+#define RT_TRY(expr)                    \
+  do {                                  \
+    const int rc_ = (expr);             \
+    if (rc_ != RT_OK) return rc_;       \
   } while (0)
 
 // The path kernel's LDS for one render (rt_trace's prologue stages these regions, in this order,
@@ -93,19 +106,21 @@ struct rt_scene {
   int n_cu = 0;                 // compute units of the device
   size_t mem_total = (size_t)8 << 30;  // device memory (hipMemGetInfo at creation)
   size_t lds_module_max = 64u << 10;  // LDS a module (hiprtc) launch may take (device limit)
-  // per kernel variant: blocks resident per CU (0 = not queried); the second half of the entries
-  // are the tile-list variants of the first
-  static constexpr int kKernelSlots = 96;
-  int resident_blocks[kKernelSlots] = {};
-  size_t resident_lds[kKernelSlots] = {};  // ... at this dynamic LDS size
-  int aov_resident[8] = {};      // the same per rt_aov variant (rt_aov.hip)
-  size_t aov_resident_lds[8] = {};
+  // per kernel launched on the scene, keyed by the kernel itself (the ahead-of-time kernel's
+  // address or the module's function handle): blocks resident per CU at this dynamic LDS size
+  // (rts::resident_blocks)
+  struct Resident {
+    const void* kernel;
+    size_t lds;
+    int blocks;
+  };
+  std::vector<Resident> resident;
   // scene-specialised product kernel (rt_jit.cpp): the generated world walker, compiled on the
   // first product render. jit_state: 0 = not compiled yet, 1 = compiled, -1 = scene not
   // generated (jit_msg says why), -2 = compile failed (jit_msg = log; the interpreter runs)
   std::string jit_walker, jit_msg;
   int jit_state = -1;
-  rtj::Kernel jit_k[8];  // [tex][staged][tile-list variant]
+  rtj::Kernel jit_k[2];  // [tile-list variant] of the scene's one variant (rt_variant.h)
   // rt_trace launch timing: one event pair per launch, ring of kTraceRing, tagged by render id
   static constexpr int kTraceRing = 4 * RT_TRACE_HISTORY;
   hipEvent_t tev[kTraceRing][2] = {};
@@ -150,6 +165,37 @@ struct SlotHold {
     sc->slot_cv.notify_all();
   }
 };
+
+// The tile-list variant (trace_body's TILES) of the ahead-of-time product kernel of variant `v`
+// (rt_tiles.hip: its 18 instances compile beside rt_device.hip's); nullptr: RT_VARIANTS has no such row.
+typedef void (*kern_t)(rtk::TraceParams);
+RTS_HIDDEN kern_t tile_trace_kernel(const rtv::Variant& v);
+
+// What every pass that launches on a scene checks of its camera and row range, with the status
+// codes and rt_last_error() texts; *sj0 / *n_sj: the call's stratum rows sj0 + k * sj_step,
+// k < n_sj (sj_step: 1, or a tile-list render's stride). path_depth: cam->max_depth is checked
+// (the AOV pass does not read it: AOVs exist at max_depth 0 too).
+RTS_HIDDEN int check_render_args(const rt_camera* cam, const rt_render_opts* opts, bool path_depth,
+                                 int sj_step, int* sj0, int* n_sj);
+
+// TraceParams of a launch on `sc` with plan LP: the scene's tables and light list, the plan's LDS
+// regions, the camera, the call's rows, seed and flags. The caller adds what only it knows: the
+// slot's queue and op counters, the chunk's stratum rows and pairs, the outputs.
+RTS_HIDDEN void fill_trace_params(rtk::TraceParams* P, const rt_scene* sc, const rt_camera* cam,
+                                  const rt_render_opts* opts, const LdsPlan& LP);
+
+// Blocks of `kernel` (module != nullptr: that module function instead) resident per CU, asked once
+// per kernel and LDS size (rt_scene::resident). A dispatch the hardware cannot place aborts the
+// whole queue, so every launch asks first; `what` names the kernel in the error text.
+RTS_HIDDEN int resident_blocks(rt_scene* sc, const void* kernel, hipFunction_t module, int block,
+                               size_t lds_bytes, const char* what, int* out);
+
+// The end of a render call that enqueued its work on `stream`: the slot's events, and with `stats`
+// the wait for the stream and the read-back. counts: samples, out_bytes and launches as the caller
+// counted them; read_ops: the launch filled the slot's op counters; t0: the call's start.
+RTS_HIDDEN int complete_render(SlotHold& hold, hipStream_t stream, rt_stats* stats,
+                               const rt_stats& counts, bool read_ops,
+                               std::chrono::steady_clock::time_point t0);
 
 // Lane item keys hold the call's row index in 15 bits (render_device_rows): taller row ranges
 // are rendered as consecutive sub-calls of kRowsPerCall rows into the matching rows of accum.

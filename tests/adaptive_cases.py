@@ -21,8 +21,8 @@ def bits(a):
 
 
 class Case:
-    def __init__(self, name):
-        scene, kw, self.flags = CASES[name]
+    def __init__(self, name, spec=None):
+        scene, kw, self.flags = spec or CASES[name]  # spec: a case of the caller's own
         self.blob, self.cam = rt.preset_blob(scene, **kw)
         self.ds = rt.DeviceScene(self.blob)
         self.H, self.W, self.S = self.cam.image_height, self.cam.image_width, self.cam.sqrt_spp

@@ -17,6 +17,15 @@ from hip_buf import DevBuf
 
 pytestmark = pytest.mark.gpu
 
+# The full-list test alone also runs the tile-list variants of two more ahead-of-time kernels (the
+# interpreter walker: no hiprtc compile), 16 x 16 each: the staged volume kernel and the staged
+# textured one.
+FULL_LIST_CASES = {
+    "smoke16": ("cornell_smoke", dict(width=16, spp=16, depth=8), rt.RT_FLAG_INTERPRETER),
+    "perlin16": ("two_perlin_spheres", dict(width=16, spp=16, depth=8, aspect=1.0),
+                 rt.RT_FLAG_INTERPRETER),
+}
+
 
 @pytest.fixture(scope="module")
 def cases(gpu_available):
@@ -24,7 +33,7 @@ def cases(gpu_available):
 
     def get(name):
         if name not in made:
-            made[name] = Case(name)
+            made[name] = Case(name, FULL_LIST_CASES.get(name))
         return made[name]
 
     yield get
@@ -32,7 +41,7 @@ def cases(gpu_available):
         c.ds.close()
 
 
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", list(CASES) + list(FULL_LIST_CASES))
 def test_full_list_stride_one_is_the_moments_render(cases, name):
     c = cases(name)
     assert (c.H, c.W) == ((12, 20) if name.startswith("cornell") else (16, 16))
