@@ -18,8 +18,8 @@
  *       /root/reference/src/render.rs:136-138, 189          added into unless RT_FLAG_OVERWRITE)
  *   panics (expect / panic!)                            int status < 0 + rt_last_error()
  *
- * Output stays host-side: write_color / the PPM writer (color.rs:8-33) are NOT behind this ABI;
- * accum holds raw per-pixel sums exactly like the reference's `pixels` vector.
+ * accum holds raw per-pixel sums exactly like the reference's `pixels` vector; auto_expose and
+ * write_color (color.rs:8-33) are rt_output* at the end of this file; the PPM writer stays host-side.
  *
  * Every entry point is plain C: pointers, sizes, PODs. No torch, no C++ types.
  */
@@ -598,6 +598,80 @@ int rt_render_adaptive(rt_adaptive* ad, rt_scene* scene, const rt_camera* cam,
                        const rt_render_opts* opts, const rt_adaptive_params* params,
                        float* accum_rgb, float* m2_rgb, float* out, float* samples,
                        uint32_t* rows_held_out, uint32_t* tiles_per_pass, rt_stats* stats);
+
+/* ---- device output stage: exposure, gamma and RGB8 ----------------------------------------------
+ * The reference's output stage (render.rs:199-213: auto_expose, then write_color per pixel,
+ * color.rs:8-59) on the device, so that a frame rendered, denoised or resolved into device memory
+ * becomes displayable bytes without a trip through the host. The host functions rth_auto_expose
+ * and rth_write_color (rt_host.h) are the single source of truth; this is their definition:
+ *
+ *   sums    height*width*3 raw f32 sums, top row first, as every render, denoise and resolve entry
+ *           point writes them (4-byte aligned). Per value, in f64 and in the host's order:
+ *             x = (double)sum * (1.0 / samples_per_pixel)
+ *             x = 1. - pow(2.718281828459045, -ev * x)           with an exposure step (color.rs:37-39)
+ *             x = x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1. / 2.4) - 0.055    (linear_to_gamma)
+ *             x = clamp to [0, 0.999]; a NaN passes the clamp
+ *             byte = Rust's saturating `as u8` of 256 * x: NaN -> 0
+ *           No product is fused into a sum. The device's pow and the host's may differ in the last
+ *           bit, so a byte can differ from rth_write_color's, by 1, only where the host's 256 * x
+ *           lies within rounding of an integer.
+ *   rgb8    height*width*3 bytes r g b, or height*width*4 bytes r g b 255 with RT_OUTPUT_RGBA; any
+ *           alignment; must not overlap sums.
+ *   ev      with RT_OUTPUT_EXPOSURE alone, params->exposure. With RT_OUTPUT_AUTO_EXPOSE, over the
+ *           N = width*height pixels, lum = 0.2126 r + 0.71516 g + 0.072169 b of the raw sums added
+ *           left to right,
+ *             m = (sum_p (1/N) * lum_p^2) / samples_per_pixel^2
+ *             ev = m > 0.001 ? -ln(0.6) / sqrt(m) : 1
+ *           The sum runs in f64 in a fixed order that depends on N alone: reduction block b owns
+ *           pixels [2048 b, 2048 (b+1)); its lane t (of 256) adds pixels 2048 b + 256 k + t for
+ *           k = 0..7 in that order; the block adds its lanes in a fixed tree (lane t += lane t + s,
+ *           s = 128, 64, .. 1); one block then adds the block sums, lane t taking blocks t, t + 256,
+ *           .. in ascending order, and the same tree. No atomics: the same inputs give the same ev
+ *           and the same bytes on every call; ev agrees with rth_auto_expose to the rounding of
+ *           two differently ordered sums of N non-negative terms. IEEE propagation gives the
+ *           host's special cases: a NaN pixel makes m NaN and ev = 1; an infinite m gives ev = 0.
+ *           ev stays in device memory, where the conversion kernel reads it: an asynchronous call
+ *           never waits on the host.
+ *
+ * A handle owns one device workspace, grown on demand (8 B per 2048 pixels: the block sums, and
+ * ev), a mutex that serialises its calls and an ordering event: each call's stream waits for the
+ * handle's previous call, whatever stream that was issued on; different handles run concurrently;
+ * rt_output_destroy waits for the handle's work. Checked before the handle is read and before any
+ * HIP call, RT_ERR_INVALID_ARG each: a null handle, params, sums or rgb8; width <= 0, height < 0,
+ * width*height >= 2^31; samples_per_pixel non-finite or <= 0; exposure non-finite with
+ * RT_OUTPUT_EXPOSURE set and RT_OUTPUT_AUTO_EXPOSE clear; unknown flag bits; _pad0 != 0.
+ * height == 0 returns RT_OK and touches no buffer. exposure_out (may be NULL) receives the ev the
+ * call applied, 0 if it had no exposure step. rt_stats: ms_kernel (events around the call's
+ * launches), ms_total, samples = pixels, launches = kernel launches (1, or 3 with auto-exposure),
+ * out_bytes = bytes written to rgb8; ops all zero.
+ *
+ * Not covered: auto-exposure over rows spread across ranks or rt_multi_* (a rank may convert its
+ * own rows with an explicit exposure it obtained elsewhere); AOV visualisation; dithering; image
+ * file encoding. */
+#define RT_OUTPUT_EXPOSURE 0x1u     /* x = 1 - E^(-exposure * x) before the gamma (color.rs:37-39)   */
+#define RT_OUTPUT_AUTO_EXPOSE 0x2u  /* exposure = auto_expose(frame) (render.rs:325-339), computed on */
+                                    /* the device; implies the exposure step; params->exposure ignored */
+#define RT_OUTPUT_RGBA 0x4u         /* 4 bytes per pixel, alpha 255; else 3 bytes per pixel           */
+
+typedef struct rt_output_params {   /* 32 bytes, no padding */
+  int32_t width, height;            /* a contiguous buffer of height rows, top row first */
+  uint32_t flags;                   /* RT_OUTPUT_*; unknown bits are RT_ERR_INVALID_ARG */
+  int32_t _pad0;                    /* must be 0 */
+  double samples_per_pixel;         /* what the sums hold (finite, > 0): scale = 1.0 / it */
+  double exposure;                  /* used with RT_OUTPUT_EXPOSURE alone; finite */
+} rt_output_params;
+
+/* opaque: device ordinal, reduction workspace, ordering event (C keeps typedef and function names
+ * in one namespace, so the handle cannot share the name of rt_output()) */
+typedef struct rt_output_stage rt_output_stage;
+int  rt_output_create(int device, rt_output_stage** out);
+void rt_output_destroy(rt_output_stage* o);
+/* asynchronous on hip_stream (may be NULL); stats != NULL or exposure_out != NULL synchronises */
+int  rt_output_device(rt_output_stage* o, const rt_output_params* p, const float* sums_dev,
+                      uint8_t* rgb8_dev, double* exposure_out, void* hip_stream, rt_stats* stats);
+/* synchronous, host buffers */
+int  rt_output(rt_output_stage* o, const rt_output_params* p, const float* sums, uint8_t* rgb8,
+               double* exposure_out, rt_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,11 @@ pub const RT_AOV_MATID: usize = 11;
 pub const RT_DENOISE_MAX_LEVELS: i32 = 8;
 pub const RT_DENOISE_DEMODULATE: u32 = 0x1;
 
+// device output stage
+pub const RT_OUTPUT_EXPOSURE: u32 = 0x1;
+pub const RT_OUTPUT_AUTO_EXPOSE: u32 = 0x2;
+pub const RT_OUTPUT_RGBA: u32 = 0x4;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -177,7 +182,19 @@ pub struct rt_adaptive_params {
     pub floor: f64,      // finite, > 0
 }
 
-/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive).
+/// Parameters of the device output stage (rt_output*); 32 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_output_params {
+    pub width: i32,
+    pub height: i32,            // a contiguous buffer of height rows, top row first
+    pub flags: u32,             // RT_OUTPUT_*
+    pub _pad0: i32,             // must be 0
+    pub samples_per_pixel: f64, // what the sums hold (finite, > 0)
+    pub exposure: f64,          // used with RT_OUTPUT_EXPOSURE alone; finite
+}
+
+/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage).
 #[repr(C)]
 pub struct rt_scene {
     _private: [u8; 0],
@@ -192,6 +209,10 @@ pub struct rt_denoiser {
 }
 #[repr(C)]
 pub struct rt_adaptive {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct rt_output_stage {
     _private: [u8; 0],
 }
 
@@ -295,4 +316,11 @@ extern "C" {
                               accum_rgb: *mut f32, m2_rgb: *mut f32, out: *mut f32,
                               samples: *mut f32, rows_held_out: *mut u32,
                               tiles_per_pass: *mut u32, stats: *mut rt_stats) -> c_int;
+    pub fn rt_output_create(device: c_int, out: *mut *mut rt_output_stage) -> c_int;
+    pub fn rt_output_destroy(o: *mut rt_output_stage);
+    pub fn rt_output_device(o: *mut rt_output_stage, p: *const rt_output_params, sums_dev: *const f32,
+                            rgb8_dev: *mut u8, exposure_out: *mut f64, hip_stream: *mut c_void,
+                            stats: *mut rt_stats) -> c_int;
+    pub fn rt_output(o: *mut rt_output_stage, p: *const rt_output_params, sums: *const f32,
+                     rgb8: *mut u8, exposure_out: *mut f64, stats: *mut rt_stats) -> c_int;
 }

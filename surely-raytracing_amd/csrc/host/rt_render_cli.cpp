@@ -7,13 +7,14 @@
 //      guided by the per-pixel variance of the row totals; needs spp >= 4)
 //   -> with --adaptive T: rt_render_adaptive (tiles stop once their estimated relative error is
 //      <= T) and the resolved frame; combines with --denoise (the filter reads the resolved frame)
-//   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]
+//   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]; with
+//      --device-output the two run on the GPU (rt_output) over whichever frame the options made
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
-//                      [--out file.ppm]
+//                      [--device-output] [--out file.ppm]
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -47,6 +48,7 @@ int main(int argc, char** argv) {
   double aspect = 0;
   uint64_t seed = 1, build_seed = 1;
   bool refsem = false, autoexp = false;
+  bool device_output = false;  // exposure, gamma and RGB8 through rt_output, not on the host
   int denoise_levels = 0;  // 0 = no denoising
   bool denoise_var = false;  // the variance-guided filter instead of the plain one
   bool adaptive = false;
@@ -95,6 +97,7 @@ int main(int argc, char** argv) {
       ad_threshold = std::atof(next());
     } else if (a == "--passes") ad_passes = std::atoi(next());
     else if (a == "--floor") ad_floor = std::atof(next());
+    else if (a == "--device-output") device_output = true;
     else if (a == "--out") out = next();
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -234,9 +237,31 @@ int main(int argc, char** argv) {
   double msps = (double)st.samples / (st.ms_kernel * 1e3);
   std::fprintf(stderr, "kernel %.2f ms, %.1f Msamples/s\n", st.ms_kernel, msps);
   int64_t n = (int64_t)cam.image_width * cam.image_height;
-  double ev = autoexp ? rth_auto_expose(accum.data(), n, cam.samples_per_pixel) : 0.0;
   std::vector<uint8_t> rgb(accum.size());
-  rth_write_color(accum.data(), n, (double)cam.samples_per_pixel, autoexp ? 1 : 0, ev, rgb.data());
+  if (device_output) {
+    rt_output_stage* os = nullptr;
+    rt_output_params op;
+    std::memset(&op, 0, sizeof(op));
+    op.width = cam.image_width;
+    op.height = cam.image_height;
+    op.flags = autoexp ? RT_OUTPUT_AUTO_EXPOSE : 0u;
+    op.samples_per_pixel = (double)cam.samples_per_pixel;
+    double ev = 0.0;
+    rt_stats st_out;
+    rc = rt_output_create(device, &os);
+    if (rc == RT_OK) rc = rt_output(os, &op, accum.data(), rgb.data(), &ev, &st_out);
+    rt_output_destroy(os);
+    if (rc != RT_OK) {
+      std::fprintf(stderr, "rt_output: %d %s\n", rc, rt_last_error());
+      return 1;
+    }
+    std::fprintf(stderr, "device output %.3f ms", st_out.ms_kernel);
+    if (autoexp) std::fprintf(stderr, ", exposure %.17g", ev);
+    std::fprintf(stderr, "\n");
+  } else {
+    double ev = autoexp ? rth_auto_expose(accum.data(), n, cam.samples_per_pixel) : 0.0;
+    rth_write_color(accum.data(), n, (double)cam.samples_per_pixel, autoexp ? 1 : 0, ev, rgb.data());
+  }
   if (rth_write_ppm(out.c_str(), rgb.data(), cam.image_width, cam.image_height) != 0) {
     std::fprintf(stderr, "%s\n", rth_last_error());
     return 1;

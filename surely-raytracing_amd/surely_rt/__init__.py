@@ -51,6 +51,11 @@ AOV_NAMES = ("hits", "t", "nx", "ny", "nz", "albedo_r", "albedo_g", "albedo_b",
 DENOISE_MAX_LEVELS = 8
 DENOISE_DEMODULATE = 0x1  # filter (beauty - emission) / max(albedo, 1e-3), re-modulate after
 
+# device output stage (rt_output*)
+RT_OUTPUT_EXPOSURE = 0x1  # x = 1 - E^(-exposure * x) before the gamma
+RT_OUTPUT_AUTO_EXPOSE = 0x2  # exposure = auto_expose(frame), computed on the device
+RT_OUTPUT_RGBA = 0x4  # 4 bytes per pixel, alpha 255; else 3
+
 OP_NAMES = [
     "samples", "world_queries", "quad_tests", "quad_plane", "quad_interval", "quad_hits",
     "sphere_tests", "sphere_roots", "sphere_hits", "aabb_tests", "translate", "rotate_y",
@@ -115,6 +120,12 @@ class RtDenoiseVarParams(C.Structure):
 class RtAdaptiveParams(C.Structure):
     _fields_ = [("passes", C.c_int32), ("min_passes", C.c_int32), ("threshold", C.c_double),
                 ("floor", C.c_double)]
+
+
+class RtOutputParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32),
+                ("_pad0", C.c_int32), ("samples_per_pixel", C.c_double),
+                ("exposure", C.c_double)]
 
 
 class RtError(RuntimeError):
@@ -263,6 +274,12 @@ def load_device_lib(path: Path) -> C.CDLL:
                                          C.POINTER(RtAdaptiveParams), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(RtStats)]),
+        "rt_output_create": (C.c_int, [C.c_int, C.POINTER(p)]),
+        "rt_output_destroy": (None, [p]),
+        "rt_output_device": (C.c_int, [p, C.POINTER(RtOutputParams), C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_double), C.c_void_p, C.POINTER(RtStats)]),
+        "rt_output": (C.c_int, [p, C.POINTER(RtOutputParams), C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_double), C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -975,6 +992,76 @@ def auto_expose(accum: np.ndarray, samples_per_pixel: int) -> float:
     """render.rs:325-339."""
     a = np.ascontiguousarray(accum, dtype=np.float32)
     return host_lib().rth_auto_expose(a.ctypes.data, a.size // 3, int(samples_per_pixel))
+
+
+def output_params(width: int, height: int, samples_per_pixel: float,
+                  exposure: float | None = None, auto: bool = False,
+                  rgba: bool = False) -> RtOutputParams:
+    """rt_output_params: exposure=None and auto=False is write_color without an exposure step;
+    auto=True computes auto_expose on the device (exposure is then ignored)."""
+    p = RtOutputParams()
+    p.width, p.height, p.samples_per_pixel = width, height, samples_per_pixel
+    p.flags = ((RT_OUTPUT_AUTO_EXPOSE if auto else 0) | (RT_OUTPUT_RGBA if rgba else 0) |
+               (RT_OUTPUT_EXPOSURE if exposure is not None and not auto else 0))
+    p.exposure = 0.0 if exposure is None or auto else exposure
+    return p
+
+
+class Output:
+    """The output stage on one GPU (rt_output_create): raw sums -> exposure, gamma, RGB8 or RGBA8,
+    with auto_expose as a fixed-order device reduction. write_color and auto_expose above stay
+    the host reference. Calls on one Output are serialised and ordered."""
+
+    def __init__(self, device: int = 0):
+        self._lib = device_lib()
+        h = C.c_void_p()
+        _check_dev(self._lib.rt_output_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rt_output_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def _has_exposure(params: RtOutputParams) -> bool:
+        return bool(params.flags & (RT_OUTPUT_EXPOSURE | RT_OUTPUT_AUTO_EXPOSE))
+
+    def output(self, sums: np.ndarray, params: RtOutputParams, stats: bool = False):
+        """Synchronous rt_output over a host array of (H, W, 3) raw sums. Returns (rgb8, ev):
+        the (H, W, 3) or, with RT_OUTPUT_RGBA, (H, W, 4) uint8 frame and the exposure applied
+        (None without an exposure step); (rgb8, ev, RtStats) with stats=True."""
+        shape = (params.height, params.width)
+        assert sums.shape == shape + (3,)
+        a = np.ascontiguousarray(sums, np.float32)
+        out = np.zeros(shape + (4 if params.flags & RT_OUTPUT_RGBA else 3,), np.uint8)
+        ev = C.c_double(0.0)
+        st = RtStats()
+        _check_dev(self._lib.rt_output(self._h, C.byref(params), a.ctypes.data, out.ctypes.data,
+                                       C.byref(ev), C.byref(st)))
+        res = (out, ev.value if self._has_exposure(params) else None)
+        return res + (st,) if stats else res
+
+    def output_device(self, params: RtOutputParams, sums_ptr: int, rgb8_ptr: int, stream: int = 0,
+                      want_exposure: bool = False, stats: bool = False):
+        """rt_output_device over device buffers: asynchronous on `stream` unless want_exposure or
+        stats, which synchronise. Returns None, the exposure applied (want_exposure; None without
+        an exposure step), RtStats (stats), or (exposure, RtStats)."""
+        ev = C.c_double(0.0) if want_exposure else None
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_output_device(
+            self._h, C.byref(params), C.c_void_p(sums_ptr), C.c_void_p(rgb8_ptr),
+            C.byref(ev) if ev is not None else None, C.c_void_p(stream or None),
+            C.byref(st) if st is not None else None))
+        res = ()
+        if want_exposure:
+            res += (ev.value if self._has_exposure(params) else None,)
+        if stats:
+            res += (st,)
+        return None if not res else res[0] if len(res) == 1 else res
 
 
 def write_ppm(path: str, rgb8: np.ndarray) -> None:
