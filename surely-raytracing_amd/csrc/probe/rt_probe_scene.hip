@@ -574,6 +574,22 @@ RTP_API int rtp_scene_records(const rt_scene_blob* blob, double* out, int cap) {
   return (int)S.recs.size();
 }
 
+// The rtl_scene_header of rtf::flatten, word by word in the struct's order (rt_layout.h), for any
+// scene the flattener takes (nested volumes and BVHs included: nothing is launched, no HIP call):
+// the bits rtv::choose_variant reads, for tests/test_variant_matrix.py. Copies at most `cap`
+// words; returns the header's size in words, or a refusal.
+RTP_API int rtp_scene_header(const rt_scene_blob* blob, uint32_t* out, int cap) {
+  static_assert(sizeof(rtl_scene_header) % sizeof(uint32_t) == 0, "rtl_scene_header: 32-bit words");
+  constexpr int kWords = (int)(sizeof(rtl_scene_header) / sizeof(uint32_t));
+  if (!blob || cap < 0 || (cap > 0 && !out)) return RTP_ERR_ARG;
+  rtf::FlatScene F;
+  std::string err;
+  const int rc = rtf::flatten(blob, &F, &err);
+  if (rc != RT_OK) return rc;
+  if (cap > 0) std::memcpy(out, &F.hdr, (size_t)(cap < kWords ? cap : kWords) * sizeof(uint32_t));
+  return kWords;
+}
+
 // The flattened material and texture tables of a scene (any scene: nothing is launched), for the
 // host test of the f32 weight mirrors (tests/test_weight_mirror.py). Copies at most *_cap words
 // each; returns the flattener's status, the table sizes in words through n_mats / n_texs.

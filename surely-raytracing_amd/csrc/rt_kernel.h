@@ -428,6 +428,13 @@ struct TraceParams {
 // The kernel's only argument sits at offset 0 of the kernarg segment. Camera constants are read
 // through this pointer at their point of use; the empty asm makes the pointer opaque so the loads
 // are not hoisted out of the path loop, where ~40 loop-invariant SGPRs would spill to VGPR lanes.
+// VALID ONLY WHERE IT IS INLINED INTO A KERNEL. A called (non-inlined) device function gets no
+// kernarg segment pointer: the callee ABI passes the implicit-argument pointer in its place and
+// the compiler lowers the builtin there to null, so a read through kparams() in such a function
+// is a read near address 0. The "nested volumes, BVH" kernels faulted this way: they are large
+// enough that the inliner left their per-lane walker in called functions. Code that may end up in
+// a called function reads its launch constants from the TraceParams reference it is handed
+// (traverse's PK).
 typedef const __attribute__((address_space(4))) TraceParams* kparams_t;
 __device__ __forceinline__ kparams_t kparams() {
   kparams_t p = (kparams_t)__builtin_amdgcn_kernarg_segment_ptr();
@@ -962,8 +969,12 @@ __device__ __forceinline__ bool prof_first_lane() {
 // walk quads whose third candidate can be needed); without it only volume_two_hits is compiled.
 // VN: ConstantMedium records nested inside volume boundaries are handled this many levels deep
 // (constant_medium.rs:46-55 queries `boundary.hit`, which may be another ConstantMedium).
+// PK: the per-lane walker reads bvh_words, bvh_lds_words and bvh_lds_off from P, not through
+// kparams(). Set for every walk of the nested-volume kernels (TravInterpN<VN > 0>), the only ones
+// so large that the inliner leaves bvh_subtree and a boundary walk as called functions, where
+// kparams() is null. PK = false instantiates the code it always did.
 template <bool MAIN, bool COUNT, bool VOL, bool UNI, bool BVH, bool VOLB = VOL, bool VOLI = true,
-          int VN = 0>
+          int VN = 0, bool PK = false>
 __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 wo, d3 wd,
                          double tm, d3 o, d3 d, int frame, double tmin, double tmax,
                          double& t_out, uint32_t& hit_node, int& hit_frame, Rng& g,
@@ -972,7 +983,8 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
 // current frame (o, d): true when the free-flight distance ends inside the boundary before
 // `closest`, with the hit t in t_hit. Shared by the interpreter walker and the generated
 // walkers of rt_jit.cpp.
-template <bool COUNT, bool UNI, bool BVH, bool VOLI, class VT = VolTwoInterp, int VN = 0>
+template <bool COUNT, bool UNI, bool BVH, bool VOLI, class VT = VolTwoInterp, int VN = 0,
+          bool PK = false>
 __device__ __forceinline__ bool volume_hit(const TraceParams& P, uint32_t node, uint4 h, d3 wo,
                                            d3 wd, double tm, d3 o, d3 d, int frame, double tmin,
                                            double closest, double& t_hit, Rng& g, Ctr<COUNT>& C,
@@ -997,9 +1009,8 @@ __device__ __forceinline__ bool volume_hit(const TraceParams& P, uint32_t node, 
       double tb;
       uint32_t dn;
       int df;
-      const bool b2 = traverse<false, COUNT, false, UNI, BVH>(P, h.w, ~0u, wo, wd, tm, o, d,
-                                                              frame, t1 + 0.0001, kInf, tb,
-                                                              dn, df, g, C);
+      const bool b2 = traverse<false, COUNT, false, UNI, BVH, false, true, 0, PK>(
+          P, h.w, ~0u, wo, wd, tm, o, d, frame, t1 + 0.0001, kInf, tb, dn, df, g, C);
       if (fb) {
         both = b2;
         t2 = tb;
@@ -1013,10 +1024,8 @@ __device__ __forceinline__ bool volume_hit(const TraceParams& P, uint32_t node, 
       int df;
       // a boundary holding ConstantMedium records (VN > 0) walks them too: their hits (and
       // random draws) are part of `boundary.hit`, in the reference's order
-      both = traverse<false, COUNT, (VN > 0), UNI, BVH, false, true, VN>(P, h.w, ~0u, wo, wd, tm,
-                                                                         o, d, frame,
-                                                                         pass ? t1 + 0.0001 : -kInf,
-                                                                         kInf, tb, dn, df, g, C);
+      both = traverse<false, COUNT, (VN > 0), UNI, BVH, false, true, VN, PK>(
+          P, h.w, ~0u, wo, wd, tm, o, d, frame, pass ? t1 + 0.0001 : -kInf, kInf, tb, dn, df, g, C);
       if (pass) t2 = tb; else t1 = tb;
     }
   }
@@ -1040,13 +1049,14 @@ __device__ __forceinline__ bool volume_hit(const TraceParams& P, uint32_t node, 
 
 // A BVH subtree [node, stop) walked per lane: its ordered BVH when it has one (obvh != 0),
 // otherwise (and always in the op-counting build) the reference tree in the reference order.
-template <bool MAIN, bool COUNT, bool VOLB, bool BVH>
+template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK = false>
 __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, uint32_t obvh,
                             d3 wo, d3 wd, double tm, d3 o, d3 d, int frame, double tmin,
                             double tmax, double& t_out, uint32_t& hit_node, int& hit_frame,
                             Rng& g, Ctr<COUNT>& C);
 
-template <bool MAIN, bool COUNT, bool VOL, bool UNI, bool BVH, bool VOLB, bool VOLI, int VN>
+template <bool MAIN, bool COUNT, bool VOL, bool UNI, bool BVH, bool VOLB, bool VOLI, int VN,
+          bool PK>
 __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 wo, d3 wd,
                          double tm, d3 o, d3 d, int frame, double tmin, double tmax,
                          double& t_out, uint32_t& hit_node, int& hit_frame, Rng& g,
@@ -1079,9 +1089,14 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
       // with every lane that has a leaf instead of interleaving with the AABB steps. BVH records
       // live in the BVH region [0, bvh_words) (rt_layout.h), so the index alone says "BVH node"
       // and no header is read; the region's first bvh_lds_words words are staged in LDS.
-      const kparams_t KP = kparams();
-      const uint32_t bvh_words = KP->bvh_words, bvh_lds = KP->bvh_lds_words;
-      const uint4* LB = reinterpret_cast<const uint4*>(rt_lds + KP->bvh_lds_off);
+      uint32_t bvh_words, bvh_lds, bvh_lds_off;
+      if constexpr (PK) {  // possibly a called function: kparams() is null there
+        bvh_words = P.bvh_words, bvh_lds = P.bvh_lds_words, bvh_lds_off = P.bvh_lds_off;
+      } else {
+        const kparams_t KP = kparams();
+        bvh_words = KP->bvh_words, bvh_lds = KP->bvh_lds_words, bvh_lds_off = KP->bvh_lds_off;
+      }
+      const uint4* LB = reinterpret_cast<const uint4*>(rt_lds + bvh_lds_off);
       auto step = [&](uint4 bh, uint4 b1, uint4 b2, uint4 b3) {
         C.inc(RT_OP_AABB_TESTS);
 #ifdef RT_PROF
@@ -1195,9 +1210,9 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
           const unsigned long long pt0 = __builtin_readcyclecounter();
           prof_steps[threadIdx.x] = 0u;
 #endif
-          const bool sub = bvh_subtree<MAIN, COUNT, VOLB, BVH>(P, node, h.y, h.w, wo, wd, tm, o,
-                                                             d, frame, tmin, closest, t, hn, hf,
-                                                             g, C);
+          const bool sub = bvh_subtree<MAIN, COUNT, VOLB, BVH, PK>(P, node, h.y, h.w, wo, wd, tm,
+                                                                 o, d, frame, tmin, closest, t,
+                                                                 hn, hf, g, C);
 #ifdef RT_PROF
           {
             const unsigned long long dt = __builtin_readcyclecounter() - pt0;
@@ -1239,7 +1254,7 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
       node = h.w;
     } else if ((MAIN || VN > 0) && VOL && type == RTL_VOLUME) {
       double tv;
-      if (volume_hit<COUNT, UNI, BVH, VOLI, VolTwoInterp, (MAIN ? VN : (VN > 0 ? VN - 1 : 0))>(
+      if (volume_hit<COUNT, UNI, BVH, VOLI, VolTwoInterp, (MAIN ? VN : (VN > 0 ? VN - 1 : 0)), PK>(
               P, node, h, wo, wd, tm, o, d, frame, tmin, closest, tv, g, C)) {
         closest = tv;
         hit = true;
@@ -1778,7 +1793,7 @@ __device__ __forceinline__ bool cbvh_walk(const TraceParams& P, uint4 hd, d3 o, 
                                                 hit_node, hit_frame, flag);
 }
 
-template <bool MAIN, bool COUNT, bool VOLB, bool BVH>
+template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK>
 __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, uint32_t obvh,
                             d3 wo, d3 wd, double tm, d3 o, d3 d, int frame, double tmin,
                             double tmax, double& t_out, uint32_t& hit_node, int& hit_frame,
@@ -1810,13 +1825,13 @@ __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, 
         h = obvh_walk<MAIN>(P, obvh, o, d, tm, frame, tmin, tmax, t_out, hit_node, hit_frame,
                             flag);
       if (__ballot(flag) != 0ull && flag)  // rare: the reference order decides
-        h = traverse<MAIN, COUNT, VOLB, false, BVH>(P, node, stop, wo, wd, tm, o, d, frame, tmin,
-                                                    tmax, t_out, hit_node, hit_frame, g, C);
+        h = traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK>(
+            P, node, stop, wo, wd, tm, o, d, frame, tmin, tmax, t_out, hit_node, hit_frame, g, C);
       return h;
     }
   }
-  return traverse<MAIN, COUNT, VOLB, false, BVH>(P, node, stop, wo, wd, tm, o, d, frame, tmin,
-                                                 tmax, t_out, hit_node, hit_frame, g, C);
+  return traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK>(
+      P, node, stop, wo, wd, tm, o, d, frame, tmin, tmax, t_out, hit_node, hit_frame, g, C);
 }
 
 // ---------------------------------------------------------------- textures
@@ -2158,9 +2173,9 @@ struct TravInterpN {
   static __device__ __forceinline__ bool world(const TraceParams& P, d3& ro, d3& rd, double tm,
                                                double& t, uint32_t& hn, int& hf, Rng& g,
                                                Ctr<COUNT>& C) {
-    return traverse<true, COUNT, VOL, true, BVH, VOLB, VOLI, VN>(P, P.root, ~0u, ro, rd, tm, ro,
-                                                                 rd, -1, 0.0001, kInf, t, hn, hf,
-                                                                 g, C);
+    // VN > 0: PK, the launch constants of the per-lane walker from P (see traverse)
+    return traverse<true, COUNT, VOL, true, BVH, VOLB, VOLI, VN, (VN > 0)>(
+        P, P.root, ~0u, ro, rd, tm, ro, rd, -1, 0.0001, kInf, t, hn, hf, g, C);
   }
   // the mixture's light-list PDF value (pdf.rs:91-93)
   template <bool COUNT>

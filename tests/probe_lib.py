@@ -75,6 +75,8 @@ def lib() -> C.CDLL:
             getattr(L, f"rtp_{name}").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.rtp_scene_records.restype = C.c_int
         L.rtp_scene_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rtp_scene_header.restype = C.c_int
+        L.rtp_scene_header.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -156,3 +158,22 @@ def scene_records(blob) -> np.ndarray:
         raise ProbeRefused("scene_records", n)
     assert n <= cap
     return out[:n].astype(np.int64)
+
+
+# rt_layout.h rtl_scene_header, word by word
+SCENE_HEADER = ("root", "n_node_words", "n_mats", "n_texs", "n_perlins", "n_lights", "lights_is_list",
+                "has_bvh", "has_volume", "max_chain", "n_texel_bytes", "pdf_materials",
+                "has_textures", "bvh_words", "volume_in_bvh", "volumes_one_walk_spheres",
+                "has_isotropic", "n_rec_words", "lights_nested", "nested_volumes", "cbvh_word0",
+                "cbvh_words", "cbvh_stack")
+
+
+def scene_header(blob) -> dict:
+    """The rtl_scene_header the product's flattener gives the scene (any scene it takes, nested
+    volumes included) -> {field: int}. Needs no GPU."""
+    out = np.zeros(len(SCENE_HEADER), np.uint32)
+    n = lib().rtp_scene_header(C.cast(blob.ref(), C.c_void_p), out.ctypes.data, out.size)
+    if n < 0:
+        raise ProbeRefused("scene_header", n)
+    assert n == len(SCENE_HEADER), f"rtl_scene_header has {n} words, SCENE_HEADER {len(SCENE_HEADER)}"
+    return {k: int(v) for k, v in zip(SCENE_HEADER, out)}

@@ -17,7 +17,9 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import probe_lib as P
 import surely_rt as rt
+import variant_scenes as V
 from hip_buf import DevBuf
 
 pytestmark = pytest.mark.gpu
@@ -151,9 +153,32 @@ def test_thin_lens_and_ragged_tiles(cornell, width, aspect):
 
 
 # ---------------------------------------------------------------- 3. depth-1 oracle render
-@pytest.mark.parametrize("name", ["cornell_smoke", "final_scene"])
+NESTED_BVH = (1, 1, 1, 0, 1, 1, 2)  # the row "nested volumes, BVH"
+UNSTAGED_FLAT = (1, 1, 0, 0, 1, 1, 0)  # the rt_variant.h row "vol, tex, no BVH, tables in global memory"
+
+
+def _depth1_scene(name):
+    """A preset at 24 x 24 x 1, or one of two scenes of variant_scenes.py with a camera of their
+    own: the flat scene with a medium and a noise texture whose tables the LDS plan does not stage
+    (the AOV pass's "no BVH, unstaged" instance), and the nest of media beside a BVH (its "BVH,
+    nested volumes" instance)."""
+    if name not in ("unstaged_flat", "nested_bvh"):
+        return rt.preset_blob(name, width=24, spp=1, aspect=1.0)
+    if name == "nested_bvh":  # the AOV pass's "BVH, nested volumes" instance
+        blob = V.build(NESTED_BVH)
+        h = P.scene_header(blob)
+        assert h["has_bvh"] == 1 and h["nested_volumes"] == 1
+    else:
+        blob = V.build(UNSTAGED_FLAT)
+        assert V.stage_scene(blob, 1)[0] == 0 and P.scene_header(blob)["has_bvh"] == 0
+    # wide enough for the lamp: every material kind is a first hit somewhere
+    cam = rt.camera_new(1.0, 24, 1, 6, 45.0, (0.3, 2.0, 9.0), (0.0, 1.6, 0.0), (0, 1, 0), 0, 0, BG)
+    return blob, cam
+
+
+@pytest.mark.parametrize("name", ["cornell_smoke", "final_scene", "unstaged_flat", "nested_bvh"])
 def test_volumes_bvh_perlin_motion_against_depth1_oracle(gpu_available, name):
-    blob, cam0 = rt.preset_blob(name, width=24, spp=1, aspect=1.0)
+    blob, cam0 = _depth1_scene(name)
     cam = _copy(cam0, background=BG)
     cam1 = _copy(cam, max_depth=1)
     W, H = cam.image_width, cam.image_height
@@ -181,8 +206,10 @@ def test_volumes_bvh_perlin_motion_against_depth1_oracle(gpu_available, name):
     print(name, "kinds", got, "misses", int((~hit).sum()))
     assert got == {k: ops[k] for k in per_kind}
     assert int((~hit).sum()) == ops["misses"] == W * H - int(aov[..., 0].sum())
-    if name == "cornell_smoke":
+    if name in ("cornell_smoke", "unstaged_flat", "nested_bvh"):
         assert ops["isotropic"] > 0  # the volumes are seen
+    if name == "unstaged_flat":
+        assert all(ops[k] > 0 for k in per_kind) and ops["noise_evals"] > 0
     ok, m = _close(aov[..., 8:11], frame)
     print(f"{name}: emission vs depth-1 oracle frame {m:.3e}")
     assert ok, m
