@@ -79,6 +79,13 @@ int rth_camera_new(double aspect_ratio, int32_t image_width, int32_t samples_per
                    const double lookat[3], const double vup[3], double defocus_angle,
                    double focus_dist, const double background[3], rt_camera* out);
 
+/* Turn a camera `degrees` about the vertical (y) axis through `pivot`, in RotateY's sense
+ * (transform.rs:143-186): center and pixel00_loc turn about the pivot, both pixel deltas and both
+ * defocus vectors about the origin. rt_camera holds only Camera's derived fields, so this is how a
+ * caller moves one (an orbit, a turntable; the camera motion rt_temporal_* reprojects across).
+ * degrees == 0 is a bitwise copy; out may be in. */
+int rth_camera_orbit_y(const rt_camera* in, const double pivot[3], double degrees, rt_camera* out);
+
 /* Scene presets restating main.rs (scene fns + their Camera::new literals). Overrides <= 0 keep
  * the reference value. variant: "" or "mixed_pdf" (cornell_box with box2 and lights = quad only,
  * the revision behind final_images/mixed_pdf.png). Names: cornell_box, cornell_smoke,

@@ -673,6 +673,129 @@ int  rt_output_device(rt_output_stage* o, const rt_output_params* p, const float
 int  rt_output(rt_output_stage* o, const rt_output_params* p, const float* sums, uint8_t* rgb8,
                double* exposure_out, rt_stats* stats);
 
+/* ---- temporal accumulation with reprojection of the frame history -------------------------------
+ * The third leg of SVGF (Schied et al. 2017) beside the variance estimate and the a-trous filter: a
+ * handle keeps the accumulated frame (the history) with the guides and the camera of the frame
+ * that wrote it; each call finds every pixel's first-hit point in world space, projects it into
+ * the previous camera, gathers the history there with a bilinear footprint whose taps on another
+ * surface are rejected, and blends history and new sample sums. Its inputs are what
+ * rt_render_moments_device and rt_render_aov_device write, its outputs raw sums in the scale that
+ * rt_denoise*, rt_denoise_var* and rt_output* take with the per-frame beauty_samples and
+ * beauty_rows unchanged.
+ *
+ * Buffers: full contiguous frames, height x width, top row first, 4-byte aligned.
+ *   beauty  H*W*3 floats, raw sums        m2   H*W*3 floats as rt_render_moments* writes them; may
+ *   aov     H*W*RT_AOV_CHANNELS floats         be NULL
+ *   cam     the camera that rendered the frame; cam->image_width and image_height must equal the
+ *           params'
+ * Guides of pixel p = (i, j), column i, row j: hits = aov[RT_AOV_HITS]; where hits > 0,
+ * z = T / hits and n = normal_sum / hits in f32, as the denoiser forms them, else z = 0, n = 0;
+ * id = aov[RT_AOV_MATID].
+ * S = the pixel's beauty sums, Q = its m2 sums. A pixel whose S (or, with m2, Q) has a non-finite
+ * component is invalid: its outputs are bitwise copies of its inputs and its history length is
+ * stored as 0, so that no later frame takes it as a tap.
+ *
+ * Reprojection, in f64 from the f32 guides:
+ *   D = pixel00_loc + i * pixel_delta_u + j * pixel_delta_v - center     (this call's camera)
+ *   X = center + z * D
+ *   M' = [pixel00_loc' - center' | pixel_delta_u' | pixel_delta_v'] as columns (previous camera)
+ *   M' (s, a, b)^T = X - center';  x' = a / s,  y' = b / s.
+ * s is the point's ray parameter in the previous camera, directly comparable with the previous
+ * frame's z: both cameras use the reference's unnormalised ray direction. The host inverts M' once
+ * per camera in f64 (adjugate over determinant); a camera whose determinant is zero or non-finite
+ * is RT_ERR_INVALID_ARG at the call that brings it. (The device forms pixel00_loc - center and
+ * center - center' on the host and adds the products to them with fused multiply-adds: the last
+ * bits of x' and y' are not specified.)
+ *
+ * Taps: i0 = floor(x'), j0 = floor(y'), fx = x' - i0, fy = y' - j0; the taps q are (i0, j0),
+ * (i0+1, j0), (i0, j0+1), (i0+1, j0+1) in that order, their weights (1-fx)(1-fy), fx(1-fy),
+ * (1-fx)fy, fx*fy formed in f64 and rounded to f32. A tap is accepted when it lies in the frame,
+ * its stored length is >= 1, its stored z_h > 0, its stored id_h == id (compared exactly),
+ * |n_h - n|^2 <= normal_tol^2 (f32) and |z_h - s| <= depth_tol * s (f64). normal_tol <= 0 switches
+ * the normal test off, depth_tol <= 0 the depth test.
+ *
+ * The history is usable at p when the handle holds a frame of the same size, p is valid with
+ * hits > 0, s, x' and y' are finite with s > 0, and Wsum, the sum of the accepted weights, is
+ * > min_weight. Then S_h, Q_h and L_h are the accepted taps' stored colour, moments and length,
+ * each weighted sum divided by Wsum, and
+ *   L = min(L_h + 1, max_history),  alpha = 1 / L,  out = (1 - alpha) * S_h + alpha * S
+ * in f32, Q blended the same way. Otherwise L = 1 and the outputs are bitwise copies of S and Q.
+ * The handle stores per pixel the blended S, the blended Q and L (0 for an invalid pixel), the
+ * frame's n, z and id, and the camera, which is the previous camera of the next call.
+ *
+ * Outputs, in the scale of the inputs: out_beauty H*W*3 (may be the beauty pointer itself);
+ * out_m2 H*W*3, required exactly when m2 is given (may equal m2); hist_len H*W floats, L per
+ * pixel (may be NULL). Any other overlap is undefined.
+ *
+ * RT_TEMPORAL_RESET discards the history before the call. RT_TEMPORAL_VARIANCE_OF_MEAN (needs m2
+ * and beauty_rows = n >= 2): where the history was used,
+ *   out_m2 = S^2 / n + max(0, Q - S^2 / n) / L   per channel,
+ * evaluated in f64 from the blended f32 values and rounded once, so that the between-row estimator
+ * above returns the variance of the accumulated mean and not of one frame: what rt_denoise_var
+ * should be guided by after accumulation. Where the history was not used (L = 1, where the
+ * expression is Q itself for every Q >= S^2 / n) out_m2 stays the bitwise copy. The handle stores
+ * the plain blended Q either way.
+ *
+ * The first call, a call with another frame size and a call with RT_TEMPORAL_RESET have no history;
+ * each starts a new one. Whether a history carries moments is fixed by the call that starts it; a
+ * later call that disagrees (m2 given against a history without moments, or the reverse) is
+ * RT_ERR_INVALID_ARG. rt_temporal_info: out[0..3] = frames accumulated since the history started,
+ * its width, its height, 1 if it carries moments.
+ *
+ * f32 arithmetic apart from the projection, the weights and the depth test; no atomics, fixed tap
+ * order: the same sequence of calls gives the same bits.
+ *
+ * A handle owns one device workspace, grown on demand: two history sets of three 16-byte records
+ * per pixel, {S, L}, {n, z}, {Q, id} (96 B per pixel), which alternate between calls; a mutex
+ * that serialises its calls and an ordering event that every call's stream waits on, whatever
+ * stream the call before went to; different handles run concurrently; rt_temporal_destroy waits
+ * for the handle's work. Checked before the handle is read and before any HIP call,
+ * RT_ERR_INVALID_ARG each: a null handle, params, camera, beauty, aov or out_beauty; width <= 0,
+ * height < 0, width*height >= 2^31; unknown flag bits; beauty_rows < 0, or < 2 with
+ * RT_TEMPORAL_VARIANCE_OF_MEAN; max_history non-finite or < 1; a non-finite tolerance; min_weight
+ * non-finite or outside [0, 1); m2 without out_m2 or the reverse; RT_TEMPORAL_VARIANCE_OF_MEAN
+ * without m2; a camera of another size or with a singular M. height == 0 returns RT_OK and
+ * touches nothing, the history included. rt_stats: ms_kernel, ms_total, samples = pixels,
+ * launches = 1, out_bytes = bytes written to the caller's buffers; ops all zero.
+ *
+ * Not covered: demodulated accumulation (albedo divided out before the blend); feeding a filtered
+ * frame back as history; motion of objects (only the camera moves; a moving Sphere's blur is inside
+ * a frame); defocus (the position is formed from center, not from the sampled origin); rows spread
+ * over ranks or rt_multi_*; adaptive frames with per-pixel sample counts. */
+#define RT_TEMPORAL_RESET 0x1u             /* discard the history before this call */
+#define RT_TEMPORAL_VARIANCE_OF_MEAN 0x2u  /* out_m2 in the scale of the accumulated mean's variance */
+
+typedef struct rt_temporal_params {   /* 32 bytes, no padding */
+  int32_t width, height;  /* a contiguous frame of height rows, top row first */
+  uint32_t flags;         /* RT_TEMPORAL_*; unknown bits are RT_ERR_INVALID_ARG */
+  int32_t beauty_rows;    /* n of the estimator; >= 2 with VARIANCE_OF_MEAN, else must be >= 0 */
+  float max_history;      /* finite, >= 1: the longest history length, alpha >= 1 / max_history */
+  float depth_tol;        /* relative; <= 0 off */
+  float normal_tol;       /* <= 0 off */
+  float min_weight;       /* finite, in [0, 1) */
+} rt_temporal_params;
+
+typedef struct rt_temporal rt_temporal;   /* opaque: device ordinal, history, camera, ordering event */
+
+/* host only: flags 0, beauty_rows 0, max_history 4, depth_tol 0.1 and normal_tol 0.3 (the
+ * denoiser's sigma_depth and sigma_normal: a neighbour more than one edge width away is another
+ * surface; max_history: the best of 4, 8, 16, 32 for accumulation followed by rt_denoise_var on
+ * cornell_box and on final_scene at 4 spp over an 8-frame orbit of 2 degrees per frame, DESIGN.md
+ * section 4.2h), min_weight 0.01 */
+int  rt_temporal_default_params(int width, int height, rt_temporal_params* out);
+int  rt_temporal_create(int device, rt_temporal** out);
+void rt_temporal_destroy(rt_temporal* t);
+int  rt_temporal_info(rt_temporal* t, uint64_t* out, int n);
+/* asynchronous on hip_stream (may be NULL); stats != NULL synchronises */
+int  rt_temporal_accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam,
+                                   const float* beauty_dev, const float* m2_dev,
+                                   const float* aov_dev, float* out_beauty_dev, float* out_m2_dev,
+                                   float* hist_len_dev, void* hip_stream, rt_stats* stats);
+/* synchronous, host buffers */
+int  rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam,
+                            const float* beauty, const float* m2, const float* aov,
+                            float* out_beauty, float* out_m2, float* hist_len, rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,10 @@ pub const RT_OUTPUT_EXPOSURE: u32 = 0x1;
 pub const RT_OUTPUT_AUTO_EXPOSE: u32 = 0x2;
 pub const RT_OUTPUT_RGBA: u32 = 0x4;
 
+// temporal accumulation
+pub const RT_TEMPORAL_RESET: u32 = 0x1;
+pub const RT_TEMPORAL_VARIANCE_OF_MEAN: u32 = 0x2;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -194,7 +198,21 @@ pub struct rt_output_params {
     pub exposure: f64,          // used with RT_OUTPUT_EXPOSURE alone; finite
 }
 
-/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage).
+/// Parameters of the temporal accumulation (rt_temporal_*); 32 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_temporal_params {
+    pub width: i32,
+    pub height: i32,      // a contiguous frame of height rows, top row first
+    pub flags: u32,       // RT_TEMPORAL_*
+    pub beauty_rows: i32, // n of the estimator; >= 2 with RT_TEMPORAL_VARIANCE_OF_MEAN, else >= 0
+    pub max_history: f32, // finite, >= 1
+    pub depth_tol: f32,   // relative; <= 0 off
+    pub normal_tol: f32,  // <= 0 off
+    pub min_weight: f32,  // finite, in [0, 1)
+}
+
+/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage, rt_temporal).
 #[repr(C)]
 pub struct rt_scene {
     _private: [u8; 0],
@@ -213,6 +231,10 @@ pub struct rt_adaptive {
 }
 #[repr(C)]
 pub struct rt_output_stage {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct rt_temporal {
     _private: [u8; 0],
 }
 
@@ -323,4 +345,19 @@ extern "C" {
                             stats: *mut rt_stats) -> c_int;
     pub fn rt_output(o: *mut rt_output_stage, p: *const rt_output_params, sums: *const f32,
                      rgb8: *mut u8, exposure_out: *mut f64, stats: *mut rt_stats) -> c_int;
+    pub fn rt_temporal_default_params(width: c_int, height: c_int,
+                                      out: *mut rt_temporal_params) -> c_int;
+    pub fn rt_temporal_create(device: c_int, out: *mut *mut rt_temporal) -> c_int;
+    pub fn rt_temporal_destroy(t: *mut rt_temporal);
+    pub fn rt_temporal_info(t: *mut rt_temporal, out: *mut u64, n: c_int) -> c_int;
+    pub fn rt_temporal_accumulate_device(t: *mut rt_temporal, p: *const rt_temporal_params,
+                                         cam: *const rt_camera, beauty_dev: *const f32,
+                                         m2_dev: *const f32, aov_dev: *const f32,
+                                         out_beauty_dev: *mut f32, out_m2_dev: *mut f32,
+                                         hist_len_dev: *mut f32, hip_stream: *mut c_void,
+                                         stats: *mut rt_stats) -> c_int;
+    pub fn rt_temporal_accumulate(t: *mut rt_temporal, p: *const rt_temporal_params,
+                                  cam: *const rt_camera, beauty: *const f32, m2: *const f32,
+                                  aov: *const f32, out_beauty: *mut f32, out_m2: *mut f32,
+                                  hist_len: *mut f32, stats: *mut rt_stats) -> c_int;
 }

@@ -212,6 +212,30 @@ int rth_camera_new(double aspect_ratio, int32_t image_width, int32_t spp, int32_
   return 0;
 }
 
+int rth_camera_orbit_y(const rt_camera* in, const double pivot[3], double degrees,
+                       rt_camera* out) {
+  if (!in || !pivot || !out || !std::isfinite(degrees)) return fail("camera_orbit_y: invalid arguments");
+  rt_camera c = *in;
+  if (degrees != 0.0) {
+    const double th = degrees * M_PI / 180.0, cs = std::cos(th), sn = std::sin(th);
+    // (x, z) -> (cs x + sn z, -sn x + cs z): RotateY's rotation (transform.rs:143-186)
+    auto turn = [&](double* v, const double* about) {
+      const double x = v[0] - about[0], z = v[2] - about[2];
+      v[0] = about[0] + (cs * x + sn * z);
+      v[2] = about[2] + (-sn * x + cs * z);
+    };
+    const double origin[3] = {0.0, 0.0, 0.0};
+    turn(c.center, pivot);
+    turn(c.pixel00_loc, pivot);
+    turn(c.pixel_delta_u, origin);
+    turn(c.pixel_delta_v, origin);
+    turn(c.defocus_disk_u, origin);
+    turn(c.defocus_disk_v, origin);
+  }
+  *out = c;
+  return 0;
+}
+
 int rth_preset(rth_scene* s, const char* name, const char* variant, int32_t width, int32_t spp,
                int32_t depth, double aspect, int32_t* world_out, int32_t* lights_out,
                rt_camera* cam_out) {

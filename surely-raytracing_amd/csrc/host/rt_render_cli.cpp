@@ -9,12 +9,18 @@
 //      <= T) and the resolved frame; combines with --denoise (the filter reads the resolved frame)
 //   -> auto_expose / write_color -> P3 PPM [render.rs:151, 199-215; color.rs:8-33]; with
 //      --device-output the two run on the GPU (rt_output) over whichever frame the options made
+//   -> with --frames N [--orbit DEG] [--temporal]: N frames, the camera turned DEG degrees per
+//      frame about the vertical axis through the centre of the world's bounding box, frame f with
+//      seed + f; each frame runs rt_render_moments, rt_render_aov, with --temporal
+//      rt_temporal_accumulate (the frame history reprojected and blended; with --denoise-var in
+//      the scale of the accumulated mean's variance), then the denoise and output options above,
+//      and is written to NAME_%03d.ppm
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
-//                      [--device-output] [--out file.ppm]
+//                      [--device-output] [--frames N] [--orbit DEG] [--temporal] [--out file.ppm]
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -42,6 +48,123 @@ static const char* scene_name(int n) {  // main.rs:715-728 selector values
   }
 }
 
+// exposure, gamma and RGB8 of one frame, on the device or on the host, and the PPM
+static int write_frame(const std::vector<float>& accum, const rt_camera& cam, bool device_output,
+                       bool autoexp, int device, const std::string& path) {
+  const int64_t n = (int64_t)cam.image_width * cam.image_height;
+  std::vector<uint8_t> rgb(accum.size());
+  if (device_output) {
+    rt_output_stage* os = nullptr;
+    rt_output_params op;
+    std::memset(&op, 0, sizeof(op));
+    op.width = cam.image_width;
+    op.height = cam.image_height;
+    op.flags = autoexp ? RT_OUTPUT_AUTO_EXPOSE : 0u;
+    op.samples_per_pixel = (double)cam.samples_per_pixel;
+    double ev = 0.0;
+    rt_stats st_out;
+    int rc = rt_output_create(device, &os);
+    if (rc == RT_OK) rc = rt_output(os, &op, accum.data(), rgb.data(), &ev, &st_out);
+    rt_output_destroy(os);
+    if (rc != RT_OK) {
+      std::fprintf(stderr, "rt_output: %d %s\n", rc, rt_last_error());
+      return 1;
+    }
+    std::fprintf(stderr, "device output %.3f ms", st_out.ms_kernel);
+    if (autoexp) std::fprintf(stderr, ", exposure %.17g", ev);
+    std::fprintf(stderr, "\n");
+  } else {
+    double ev = autoexp ? rth_auto_expose(accum.data(), n, cam.samples_per_pixel) : 0.0;
+    rth_write_color(accum.data(), n, (double)cam.samples_per_pixel, autoexp ? 1 : 0, ev, rgb.data());
+  }
+  if (rth_write_ppm(path.c_str(), rgb.data(), cam.image_width, cam.image_height) != 0) {
+    std::fprintf(stderr, "%s\n", rth_last_error());
+    return 1;
+  }
+  return 0;
+}
+
+// --frames: the orbit. Every frame: moments, AOVs, the temporal accumulation, the filter, the
+// output stage, NAME_%03d.ppm.
+static int render_frames(const rt_scene_blob& blob, const rt_camera& cam0, rt_render_opts o,
+                         const double pivot[3], int frames, double orbit, bool temporal,
+                         int denoise_levels, bool denoise_var, bool device_output, bool autoexp,
+                         const std::string& out) {
+  const int W = cam0.image_width, H = cam0.image_height;
+  const size_t n_px = (size_t)W * H;
+  std::vector<float> accum(n_px * 3, 0.f), m2(n_px * 3, 0.f), aov(n_px * RT_AOV_CHANNELS, 0.f);
+  std::vector<float> len(n_px, 0.f);
+  rt_scene* sc = nullptr;
+  rt_temporal* tp = nullptr;
+  rt_denoiser* dn = nullptr;
+  rt_temporal_params tpar;
+  rt_denoise_params dp;
+  rt_denoise_var_params dvp;
+  int rc = rt_scene_create(&blob, o.device, &sc);
+  if (rc == RT_OK && temporal) rc = rt_temporal_create(o.device, &tp);
+  if (rc == RT_OK && temporal) rc = rt_temporal_default_params(W, H, &tpar);
+  if (rc == RT_OK && temporal) {
+    tpar.beauty_rows = cam0.sqrt_spp;
+    if (denoise_levels && denoise_var) tpar.flags |= RT_TEMPORAL_VARIANCE_OF_MEAN;
+  }
+  if (rc == RT_OK && denoise_levels) rc = rt_denoiser_create(o.device, &dn);
+  if (rc == RT_OK && denoise_levels && denoise_var) {
+    rc = rt_denoise_var_default_params(W, H, cam0.samples_per_pixel, cam0.sqrt_spp,
+                                       cam0.samples_per_pixel, &dvp);
+    if (rc == RT_OK && denoise_levels > 0) dvp.levels = denoise_levels;
+  } else if (rc == RT_OK && denoise_levels) {
+    rc = rt_denoise_default_params(W, H, cam0.samples_per_pixel, cam0.samples_per_pixel, &dp);
+    if (rc == RT_OK && denoise_levels > 0) dp.levels = denoise_levels;
+  }
+  const std::string::size_type dot = out.rfind('.');
+  const std::string stem = dot == std::string::npos ? out : out.substr(0, dot);
+  const std::string ext = dot == std::string::npos ? "" : out.substr(dot);
+  const uint64_t seed0 = o.seed;
+  int status = 0;
+  for (int f = 0; rc == RT_OK && status == 0 && f < frames; ++f) {
+    rt_camera cam;
+    if (rth_camera_orbit_y(&cam0, pivot, orbit * f, &cam) != 0) {
+      std::fprintf(stderr, "%s\n", rth_last_error());
+      status = 1;
+      break;
+    }
+    o.seed = seed0 + (uint64_t)f;
+    rt_stats st, st_aov, st_tp, st_dn;
+    std::memset(&st_aov, 0, sizeof(st_aov));
+    std::memset(&st_tp, 0, sizeof(st_tp));
+    std::memset(&st_dn, 0, sizeof(st_dn));
+    rc = rt_render_moments(sc, &cam, &o, accum.data(), m2.data(), &st);
+    if (rc == RT_OK && (temporal || denoise_levels)) rc = rt_render_aov(sc, &cam, &o, aov.data(), &st_aov);
+    double reused = 0.0;
+    if (rc == RT_OK && temporal) {
+      rc = rt_temporal_accumulate(tp, &tpar, &cam, accum.data(), m2.data(), aov.data(),
+                                  accum.data(), m2.data(), len.data(), &st_tp);
+      for (float l : len) reused += l > 1.f ? 1.0 : 0.0;
+    }
+    if (rc == RT_OK && denoise_levels && denoise_var)
+      rc = rt_denoise_var(dn, &dvp, accum.data(), m2.data(), aov.data(), accum.data(), nullptr,
+                          &st_dn);
+    else if (rc == RT_OK && denoise_levels)
+      rc = rt_denoise(dn, &dp, accum.data(), aov.data(), accum.data(), &st_dn);
+    if (rc != RT_OK) break;
+    std::fprintf(stderr,
+                 "frame %d: kernel %.2f ms, aov %.2f ms, temporal %.3f ms (history at %.1f %% of "
+                 "the pixels), denoise %.3f ms\n",
+                 f, st.ms_kernel, st_aov.ms_kernel, st_tp.ms_kernel, 100.0 * reused / (double)n_px,
+                 st_dn.ms_kernel);
+    char num[16];
+    std::snprintf(num, sizeof(num), "_%03d", f);
+    const std::string path = stem + num + ext;
+    status = write_frame(accum, cam, device_output, autoexp, o.device, path);
+    if (status == 0) std::fprintf(stderr, "wrote %s\n", path.c_str());
+  }
+  if (rc != RT_OK) std::fprintf(stderr, "rt_render --frames: %d %s\n", rc, rt_last_error());
+  rt_denoiser_destroy(dn);
+  rt_temporal_destroy(tp);
+  rt_scene_destroy(sc);
+  return rc != RT_OK ? 1 : status;
+}
+
 int main(int argc, char** argv) {
   std::string scene = "cornell_box", variant, out = "image.ppm";
   int width = 0, spp = 0, depth = 0, device = 0;
@@ -54,6 +177,9 @@ int main(int argc, char** argv) {
   bool adaptive = false;
   double ad_threshold = 0.0, ad_floor = 1e-2;
   int ad_passes = 0;  // 0 = min(8, sqrt_spp / 2)
+  int frames = 0;  // 0 = one frame, written to --out itself
+  double orbit = 0.0;  // degrees per frame
+  bool temporal = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -98,6 +224,9 @@ int main(int argc, char** argv) {
     } else if (a == "--passes") ad_passes = std::atoi(next());
     else if (a == "--floor") ad_floor = std::atof(next());
     else if (a == "--device-output") device_output = true;
+    else if (a == "--frames") frames = std::atoi(next());
+    else if (a == "--orbit") orbit = std::atof(next());
+    else if (a == "--temporal") temporal = true;
     else if (a == "--out") out = next();
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -109,6 +238,12 @@ int main(int argc, char** argv) {
                  "--adaptive does not combine with --denoise-var: that filter takes one beauty_rows "
                  "for the whole frame, and an adaptive frame holds a different number of stratum "
                  "rows per tile (use --denoise, which reads the resolved frame)\n");
+    return 2;
+  }
+  if (frames < 0 || ((orbit != 0.0 || temporal) && frames == 0) || (frames && adaptive)) {
+    std::fprintf(stderr,
+                 "--orbit and --temporal need --frames N (N >= 1); --frames does not combine with "
+                 "--adaptive (rt_temporal takes one sample count for the whole frame)\n");
     return 2;
   }
   rth_scene* s = rth_scene_new(build_seed);
@@ -135,6 +270,19 @@ int main(int argc, char** argv) {
   o.n_rows = cam.image_height;
   o.flags = RT_FLAG_OVERWRITE | (refsem ? RT_FLAG_SEMANTICS_REFERENCE : 0u);
   o.device = device;
+  if (frames) {
+    double box[6];
+    if (rth_object_bbox(s, world, box) != 0) {
+      std::fprintf(stderr, "bbox: %s\n", rth_last_error());
+      return 1;
+    }
+    const double pivot[3] = {0.5 * (box[0] + box[1]), 0.5 * (box[2] + box[3]),
+                             0.5 * (box[4] + box[5])};
+    const int status = render_frames(blob, cam, o, pivot, frames, orbit, temporal, denoise_levels,
+                                     denoise_var, device_output, autoexp, out);
+    rth_scene_free(s);
+    return status;
+  }
   std::vector<float> accum((size_t)cam.image_width * cam.image_height * 3, 0.f);
   rt_stats st;
   int rc;
@@ -236,36 +384,7 @@ int main(int argc, char** argv) {
   }
   double msps = (double)st.samples / (st.ms_kernel * 1e3);
   std::fprintf(stderr, "kernel %.2f ms, %.1f Msamples/s\n", st.ms_kernel, msps);
-  int64_t n = (int64_t)cam.image_width * cam.image_height;
-  std::vector<uint8_t> rgb(accum.size());
-  if (device_output) {
-    rt_output_stage* os = nullptr;
-    rt_output_params op;
-    std::memset(&op, 0, sizeof(op));
-    op.width = cam.image_width;
-    op.height = cam.image_height;
-    op.flags = autoexp ? RT_OUTPUT_AUTO_EXPOSE : 0u;
-    op.samples_per_pixel = (double)cam.samples_per_pixel;
-    double ev = 0.0;
-    rt_stats st_out;
-    rc = rt_output_create(device, &os);
-    if (rc == RT_OK) rc = rt_output(os, &op, accum.data(), rgb.data(), &ev, &st_out);
-    rt_output_destroy(os);
-    if (rc != RT_OK) {
-      std::fprintf(stderr, "rt_output: %d %s\n", rc, rt_last_error());
-      return 1;
-    }
-    std::fprintf(stderr, "device output %.3f ms", st_out.ms_kernel);
-    if (autoexp) std::fprintf(stderr, ", exposure %.17g", ev);
-    std::fprintf(stderr, "\n");
-  } else {
-    double ev = autoexp ? rth_auto_expose(accum.data(), n, cam.samples_per_pixel) : 0.0;
-    rth_write_color(accum.data(), n, (double)cam.samples_per_pixel, autoexp ? 1 : 0, ev, rgb.data());
-  }
-  if (rth_write_ppm(out.c_str(), rgb.data(), cam.image_width, cam.image_height) != 0) {
-    std::fprintf(stderr, "%s\n", rth_last_error());
-    return 1;
-  }
+  if (write_frame(accum, cam, device_output, autoexp, device, out) != 0) return 1;
   std::fprintf(stderr, "Done! wrote %s\n", out.c_str());
   rth_scene_free(s);
   return 0;

@@ -56,6 +56,10 @@ RT_OUTPUT_EXPOSURE = 0x1  # x = 1 - E^(-exposure * x) before the gamma
 RT_OUTPUT_AUTO_EXPOSE = 0x2  # exposure = auto_expose(frame), computed on the device
 RT_OUTPUT_RGBA = 0x4  # 4 bytes per pixel, alpha 255; else 3
 
+# temporal accumulation (rt_temporal_*)
+RT_TEMPORAL_RESET = 0x1  # discard the history before the call
+RT_TEMPORAL_VARIANCE_OF_MEAN = 0x2  # out_m2 in the scale of the accumulated mean's variance
+
 OP_NAMES = [
     "samples", "world_queries", "quad_tests", "quad_plane", "quad_interval", "quad_hits",
     "sphere_tests", "sphere_roots", "sphere_hits", "aabb_tests", "translate", "rotate_y",
@@ -128,6 +132,12 @@ class RtOutputParams(C.Structure):
                 ("exposure", C.c_double)]
 
 
+class RtTemporalParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32),
+                ("beauty_rows", C.c_int32), ("max_history", C.c_float), ("depth_tol", C.c_float),
+                ("normal_tol", C.c_float), ("min_weight", C.c_float)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rt error {code}: {msg}")
@@ -189,6 +199,7 @@ def host_lib() -> C.CDLL:
             "rth_serialize": (C.c_int, [p, i32, i32, C.POINTER(RtSceneBlob)]),
             "rth_camera_new": (C.c_int, [f64, i32, i32, i32, f64, dp, dp, dp, f64, f64, dp,
                                          C.POINTER(RtCamera)]),
+            "rth_camera_orbit_y": (C.c_int, [C.POINTER(RtCamera), dp, f64, C.POINTER(RtCamera)]),
             "rth_preset": (C.c_int, [p, C.c_char_p, C.c_char_p, i32, i32, i32, f64,
                                      C.POINTER(i32), C.POINTER(i32), C.POINTER(RtCamera)]),
             "rth_auto_expose": (f64, [C.c_void_p, C.c_int64, i32]),
@@ -280,6 +291,17 @@ def load_device_lib(path: Path) -> C.CDLL:
                                        C.POINTER(C.c_double), C.c_void_p, C.POINTER(RtStats)]),
         "rt_output": (C.c_int, [p, C.POINTER(RtOutputParams), C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_double), C.POINTER(RtStats)]),
+        "rt_temporal_default_params": (C.c_int, [C.c_int, C.c_int, C.POINTER(RtTemporalParams)]),
+        "rt_temporal_create": (C.c_int, [C.c_int, C.POINTER(p)]),
+        "rt_temporal_destroy": (None, [p]),
+        "rt_temporal_info": (C.c_int, [p, C.POINTER(C.c_uint64), C.c_int]),
+        "rt_temporal_accumulate_device": (C.c_int, [p, C.POINTER(RtTemporalParams),
+                                                    C.POINTER(RtCamera), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_temporal_accumulate": (C.c_int, [p, C.POINTER(RtTemporalParams), C.POINTER(RtCamera),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
         "rt_render_blob": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(RtCamera),
                                      C.POINTER(RtRenderOpts), C.c_void_p,
                                      C.POINTER(RtStats)]),
@@ -496,6 +518,16 @@ def camera_new(aspect_ratio, image_width, samples_per_pixel, max_depth, vfov, lo
                                           defocus_angle, focus_dist, _d3(background),
                                           C.byref(cam)))
     return cam
+
+
+def camera_orbit_y(cam: RtCamera, pivot, degrees: float) -> RtCamera:
+    """rth_camera_orbit_y: `cam` turned `degrees` about the vertical axis through `pivot` (center
+    and pixel00_loc about the pivot, the pixel deltas and defocus vectors about the origin).
+    0 degrees is a bitwise copy."""
+    out = RtCamera()
+    _check_host(host_lib().rth_camera_orbit_y(C.byref(cam), _d3(pivot), float(degrees),
+                                              C.byref(out)))
+    return out
 
 
 def preset_blob(name: str, variant: str = "", width: int = 0, spp: int = 0, depth: int = 0,
@@ -762,6 +794,80 @@ class Denoiser:
         _check_dev(self._lib.rt_denoise_var_device(
             self._h, C.byref(params), C.c_void_p(beauty_ptr), C.c_void_p(m2_ptr),
             C.c_void_p(aov_ptr), C.c_void_p(out_ptr), C.c_void_p(var_out_ptr or None),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
+        return st
+
+
+# ---------------------------------------------------------------------------- temporal accumulation
+def temporal_default_params(width: int, height: int) -> RtTemporalParams:
+    """rt_temporal_default_params (host only): no flags, beauty_rows 0, max_history 4, depth_tol
+    0.1, normal_tol 0.3, min_weight 0.01."""
+    p = RtTemporalParams()
+    _check_dev(device_lib().rt_temporal_default_params(width, height, C.byref(p)))
+    return p
+
+
+class Temporal:
+    """Temporal accumulation on one GPU (rt_temporal_create): the handle keeps the accumulated
+    frame, its guides and its camera, and each accumulate() reprojects that history into the new
+    frame and blends. Calls on one Temporal are serialised and ordered; several run concurrently."""
+
+    def __init__(self, device: int = 0):
+        self._lib = device_lib()
+        h = C.c_void_p()
+        _check_dev(self._lib.rt_temporal_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rt_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self) -> dict:
+        out = (C.c_uint64 * 4)()
+        _check_dev(self._lib.rt_temporal_info(self._h, out, 4))
+        return dict(frames=int(out[0]), width=int(out[1]), height=int(out[2]),
+                    moments=bool(out[3]))
+
+    def accumulate(self, cam: RtCamera, beauty: np.ndarray, aov: np.ndarray,
+                   params: RtTemporalParams, m2: np.ndarray | None = None,
+                   hist_len: bool = False, stats: bool = False):
+        """Synchronous rt_temporal_accumulate over host arrays: beauty (and m2) (H, W, 3) as
+        render_moments() returns them, aov as render_aov() returns it, cam the camera that
+        rendered them. Returns the accumulated beauty, followed by the accumulated m2 when m2 is
+        given, by the (H, W) history lengths with hist_len=True and by RtStats with stats=True."""
+        shape = (params.height, params.width)
+        assert beauty.shape == shape + (3,) and aov.shape == shape + (AOV_CHANNELS,)
+        assert m2 is None or m2.shape == shape + (3,)
+        b = np.ascontiguousarray(beauty, np.float32)
+        a = np.ascontiguousarray(aov, np.float32)
+        q = None if m2 is None else np.ascontiguousarray(m2, np.float32)
+        out = np.zeros(shape + (3,), np.float32)
+        out_q = None if m2 is None else np.zeros(shape + (3,), np.float32)
+        ln = np.zeros(shape, np.float32) if hist_len else None
+        st = RtStats()
+        _check_dev(self._lib.rt_temporal_accumulate(
+            self._h, C.byref(params), C.byref(cam), b.ctypes.data,
+            None if q is None else q.ctypes.data, a.ctypes.data, out.ctypes.data,
+            None if out_q is None else out_q.ctypes.data, None if ln is None else ln.ctypes.data,
+            C.byref(st)))
+        res = ((out,) + ((out_q,) if m2 is not None else ()) + ((ln,) if hist_len else ()) +
+               ((st,) if stats else ()))
+        return res if len(res) > 1 else out
+
+    def accumulate_device(self, params: RtTemporalParams, cam: RtCamera, beauty_ptr: int,
+                          aov_ptr: int, out_beauty_ptr: int, m2_ptr: int = 0, out_m2_ptr: int = 0,
+                          hist_len_ptr: int = 0, stream: int = 0, stats: bool = False):
+        """Asynchronous rt_temporal_accumulate_device over device buffers (out_beauty_ptr may equal
+        beauty_ptr, out_m2_ptr may equal m2_ptr; 0 = not given)."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_temporal_accumulate_device(
+            self._h, C.byref(params), C.byref(cam), C.c_void_p(beauty_ptr),
+            C.c_void_p(m2_ptr or None), C.c_void_p(aov_ptr), C.c_void_p(out_beauty_ptr),
+            C.c_void_p(out_m2_ptr or None), C.c_void_p(hist_len_ptr or None),
             C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
 
