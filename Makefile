@@ -18,7 +18,7 @@ CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 CFLAGS_O := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function
 
 HOST_SRC := $(CSRC)/host/scene.cpp $(CSRC)/host/presets.cpp $(CSRC)/host/capi.cpp
-DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
+DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
 DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
@@ -41,7 +41,7 @@ $(BUILD)/rt_jit_sources.inc: $(JIT_HDR) $(CSRC)/embed_sources.py
 # one object per source, so an edit of the host-side generator or flattener does not recompile
 # the kernels (rt_device.hip: every ahead-of-time template instance, ~3 minutes)
 OBJ      := $(BUILD)/obj
-DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_aov.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
+DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_aov.o $(OBJ)/rt_query.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
 $(OBJ)/rt_device.o: $(CSRC)/rt_device.hip $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -60,6 +60,10 @@ $(OBJ)/rt_output.o: $(CSRC)/rt_output.hip $(DEV_HDR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the first-hit AOV kernels (rt_aov.h is ahead-of-time only: not one of JIT_HDR)
 $(OBJ)/rt_aov.o: $(CSRC)/rt_aov.hip $(CSRC)/rt_aov.h $(DEV_HDR)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# the ray-query kernels (rt_query.h is ahead-of-time only: not one of JIT_HDR)
+$(OBJ)/rt_query.o: $(CSRC)/rt_query.hip $(CSRC)/rt_query.h $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the a-trous denoisers (rt_denoise.h is ahead-of-time only: not in JIT_HDR)

@@ -796,6 +796,88 @@ int  rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const r
                             const float* beauty, const float* m2, const float* aov,
                             float* out_beauty, float* out_m2, float* hist_len, rt_stats* stats);
 
+/* ---- ray queries: closest hits for caller-supplied rays -----------------------------------------
+ * What does this ray hit? Every other entry point forms its rays from an rt_camera; this one takes
+ * them from the caller, so picking, depth or visibility for camera models rt_camera cannot express
+ * (orthographic, fisheye, panoramas, lidar patterns), ambient-occlusion or shadow-ray batches and
+ * geometric checks of a scene need no second ray tracer.
+ *
+ * Each ray runs ONE world.hit(r, Interval{tmin, tmax}) (hittable.rs:88-109) through the interpreter
+ * walker, exactly as the AOV pass runs its query: the scene's ordered BVHs are walked from LDS, or
+ * the reference tree in the reference's order under RT_FLAG_REFERENCE_BVH (same records, bit for
+ * bit). The interval ends are the reference's: a Quad accepts t == tmin and t == tmax (object.rs:
+ * 462), a Sphere's root must lie strictly inside (object.rs:156-163), and of two quads at the same
+ * t the later one in the list wins. A ConstantMedium's free-flight draw comes from a generator
+ * freshly seeded with rng_seed(params->seed, ray.pixel, ray.sample), the keying of the render
+ * passes; scenes without media ignore seed, pixel and sample. A ray's record depends on that ray
+ * and the params alone: not on its place in the batch, its neighbours or n_rays.
+ *
+ * prim: the place of the hit primitive among the world's spheres, quads and ConstantMediums in the
+ * blob's pre-order (a ConstantMedium's boundary primitives are counted after it), so a caller can
+ * map it back to the object it serialised. It is the primitive the reference's own hit record
+ * comes from. That matters in one case: a BvhNode over a span of one leaf holds the leaf twice
+ * (hittable.rs:161-162) and re-tests it over [tmin, rec.t]; a quad's inclusive interval accepts
+ * again, so the reference's record is the second copy's, while a sphere's strict one is the first
+ * copy's. rt_scene_prim_map returns the table behind it, by leaf-record word offset of the
+ * flattened node array, ascending in word: every QUAD, SPHERE and VOLUME record of the world is
+ * listed, the copies a BvhNode layout duplicates included, and the prims are exactly 0 .. n-1. In
+ * a duplicated quad pair the first copy's record (the one the walker reports) carries the second
+ * copy's prim and the second copy's record the first's. *n_out is the entry count even if cap is
+ * smaller; at most cap entries are written. rt_scene_create keeps the table; the scene's first
+ * query uploads it, under the scene mutex.
+ *
+ * Invalid rays: a non-finite origin, dir or time component, a dir that is all zero, a NaN tmin or
+ * tmax, an infinite tmin. Such a ray never reaches the walker (its lane walks a fixed harmless ray
+ * with its wave); its record is hit = -1 and every other field 0, in occlusion mode the byte 255.
+ * The other rays' records are unaffected and the call returns RT_OK.
+ *
+ * Checked before the scene is read and before any HIP call, RT_ERR_INVALID_ARG each: a null scene,
+ * params, rays or out; n_rays >= 2^31; flag bits other than RT_FLAG_REFERENCE_BVH; mode bits other
+ * than RT_QUERY_OCCLUSION; rays not 16-byte aligned; out not 16-byte aligned in record mode.
+ * n_rays == 0 returns RT_OK and touches nothing. Slots, stream ordering, re-entrancy and lifetime
+ * are those of rt_render_aov_device. rt_stats: ms_kernel, ms_total; samples = n_rays; launches = 1;
+ * out_bytes = bytes written (80 or 1 per ray); ops all zero.
+ *
+ * Not covered: an any-hit early exit (occlusion mode runs the closest-hit walk and writes less);
+ * u, v, albedo or emission at the hit; the scene-specialised hiprtc walker, whose interval is
+ * fixed; rt_multi_*. */
+typedef struct rt_ray {        /* 80 bytes, no padding */
+  double origin[3];
+  double dir[3];               /* not normalised: t is the ray parameter, as everywhere in this ABI */
+  double time;                 /* Ray::time: a moving Sphere's centre */
+  double tmin, tmax;           /* the interval handed to world.hit; tmax may be +inf */
+  uint32_t pixel, sample;      /* the ray's random stream: rng_seed(params->seed, pixel, sample) */
+} rt_ray;
+
+typedef struct rt_hit {        /* 80 bytes, no padding */
+  double t;                    /* rec.t; the ray's own tmax on a miss; 0 for an invalid ray */
+  double distance;             /* t * sqrt(dir . dir), f64; 0 unless hit == 1 */
+  double p[3];                 /* rec.p, world space; 0 unless hit == 1 */
+  double normal[3];            /* rec.normal after set_face_normal, world space; a ConstantMedium hit has (1,0,0) */
+  int32_t hit;                 /* 1 hit, 0 miss, -1 invalid ray */
+  int32_t front_face;          /* rec.front_face (1 for a ConstantMedium hit); 0 unless hit == 1 */
+  int32_t material;            /* blob material-table index; -1 on a miss, 0 for an invalid ray */
+  int32_t prim;                /* see above; -1 on a miss, 0 for an invalid ray */
+} rt_hit;
+
+#define RT_QUERY_OCCLUSION 0x1u   /* out is one uint8 per ray: 1 hit, 0 miss, 255 invalid */
+
+typedef struct rt_query_params {  /* 16 bytes */
+  uint64_t seed;
+  uint32_t flags;              /* RT_FLAG_REFERENCE_BVH only; any other RT_FLAG_* bit is RT_ERR_INVALID_ARG */
+  uint32_t mode;               /* 0 or RT_QUERY_OCCLUSION; unknown bits RT_ERR_INVALID_ARG */
+} rt_query_params;
+
+/* asynchronous on hip_stream (may be NULL): device buffers; stats != NULL synchronises */
+int rt_query_rays_device(rt_scene* scene, const rt_query_params* params, const rt_ray* rays_dev,
+                         uint64_t n_rays, void* out_dev, void* hip_stream, rt_stats* stats);
+/* synchronous, host buffers */
+int rt_query_rays(rt_scene* scene, const rt_query_params* params, const rt_ray* rays,
+                  uint64_t n_rays, void* out, rt_stats* stats);
+/* host only, no device: the table behind rt_hit.prim */
+int rt_scene_prim_map(const rt_scene_blob* blob, uint32_t* node_word, uint32_t* prim, uint32_t cap,
+                      uint32_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

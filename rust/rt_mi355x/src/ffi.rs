@@ -79,6 +79,9 @@ pub const RT_OUTPUT_RGBA: u32 = 0x4;
 pub const RT_TEMPORAL_RESET: u32 = 0x1;
 pub const RT_TEMPORAL_VARIANCE_OF_MEAN: u32 = 0x2;
 
+// ray queries
+pub const RT_QUERY_OCCLUSION: u32 = 0x1;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -210,6 +213,42 @@ pub struct rt_temporal_params {
     pub depth_tol: f32,   // relative; <= 0 off
     pub normal_tol: f32,  // <= 0 off
     pub min_weight: f32,  // finite, in [0, 1)
+}
+
+/// A caller-supplied ray of rt_query_rays*; 80 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_ray {
+    pub origin: [f64; 3],
+    pub dir: [f64; 3], // not normalised: t is the ray parameter
+    pub time: f64,     // Ray::time: a moving Sphere's centre
+    pub tmin: f64,     // the interval handed to world.hit; tmax may be +inf
+    pub tmax: f64,
+    pub pixel: u32,    // the ray's random stream: rng_seed(params.seed, pixel, sample)
+    pub sample: u32,
+}
+
+/// The closest hit of one ray (rt_query_rays*); 80 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_hit {
+    pub t: f64,            // rec.t; the ray's own tmax on a miss; 0 for an invalid ray
+    pub distance: f64,     // t * sqrt(dir . dir); 0 unless hit == 1
+    pub p: [f64; 3],       // rec.p, world space; 0 unless hit == 1
+    pub normal: [f64; 3],  // rec.normal after set_face_normal; 0 unless hit == 1
+    pub hit: i32,          // 1 hit, 0 miss, -1 invalid ray
+    pub front_face: i32,   // rec.front_face; 0 unless hit == 1
+    pub material: i32,     // blob material-table index; -1 on a miss, 0 for an invalid ray
+    pub prim: i32,         // place among the world's primitives; -1 on a miss, 0 for an invalid ray
+}
+
+/// Parameters of rt_query_rays*; 16 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_query_params {
+    pub seed: u64,
+    pub flags: u32, // RT_FLAG_REFERENCE_BVH only
+    pub mode: u32,  // 0 or RT_QUERY_OCCLUSION
 }
 
 /// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage, rt_temporal).
@@ -360,4 +399,12 @@ extern "C" {
                                   cam: *const rt_camera, beauty: *const f32, m2: *const f32,
                                   aov: *const f32, out_beauty: *mut f32, out_m2: *mut f32,
                                   hist_len: *mut f32, stats: *mut rt_stats) -> c_int;
+    pub fn rt_query_rays_device(scene: *mut rt_scene, params: *const rt_query_params,
+                                rays_dev: *const rt_ray, n_rays: u64, out_dev: *mut c_void,
+                                hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_query_rays(scene: *mut rt_scene, params: *const rt_query_params,
+                         rays: *const rt_ray, n_rays: u64, out: *mut c_void,
+                         stats: *mut rt_stats) -> c_int;
+    pub fn rt_scene_prim_map(blob: *const rt_scene_blob, node_word: *mut u32, prim: *mut u32,
+                             cap: u32, n_out: *mut u32) -> c_int;
 }

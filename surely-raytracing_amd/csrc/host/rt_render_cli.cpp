@@ -15,14 +15,18 @@
 //      rt_temporal_accumulate (the frame history reprojected and blended; with --denoise-var in
 //      the scale of the accumulated mean's variance), then the denoise and output options above,
 //      and is written to NAME_%03d.ppm
+//   -> with --pick X Y: no render; rt_query_rays with the pixel-centre ray of the preset's camera,
+//      `hit t distance p normal front material prim` on one line of stdout
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
 //                      [--device-output] [--frames N] [--orbit DEG] [--temporal] [--out file.ppm]
+//                      [--pick X Y]
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -165,6 +169,44 @@ static int render_frames(const rt_scene_blob& blob, const rt_camera& cam0, rt_re
   return rc != RT_OK ? 1 : status;
 }
 
+// --pick X Y: the ray from the camera centre through the centre of pixel (X, Y) (no jitter, no
+// defocus, time 0), one rt_query_rays over [1e-4, inf), one line on stdout:
+//   hit t distance p normal front material prim
+static int pick_pixel(const rt_scene_blob& blob, const rt_camera& cam, int x, int y, uint64_t seed,
+                      int device) {
+  if (x < 0 || y < 0 || x >= cam.image_width || y >= cam.image_height) {
+    std::fprintf(stderr, "--pick %d %d: outside the %dx%d image\n", x, y, cam.image_width,
+                 cam.image_height);
+    return 2;
+  }
+  alignas(16) rt_ray r;  // the query takes 16-byte aligned records
+  std::memset(&r, 0, sizeof(r));
+  for (int k = 0; k < 3; ++k) {
+    r.origin[k] = cam.center[k];
+    r.dir[k] = cam.pixel00_loc[k] + x * cam.pixel_delta_u[k] + y * cam.pixel_delta_v[k] -
+               cam.center[k];
+  }
+  r.tmin = 1e-4;
+  r.tmax = HUGE_VAL;
+  r.pixel = (uint32_t)(y * cam.image_width + x);
+  rt_query_params qp;
+  std::memset(&qp, 0, sizeof(qp));
+  qp.seed = seed;
+  alignas(16) rt_hit h;
+  rt_scene* sc = nullptr;
+  int rc = rt_scene_create(&blob, device, &sc);
+  if (rc == RT_OK) rc = rt_query_rays(sc, &qp, &r, 1, &h, nullptr);
+  rt_scene_destroy(sc);
+  if (rc != RT_OK) {
+    std::fprintf(stderr, "rt_query_rays: %d %s\n", rc, rt_last_error());
+    return 1;
+  }
+  std::printf("%d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %d %d\n", h.hit, h.t,
+              h.distance, h.p[0], h.p[1], h.p[2], h.normal[0], h.normal[1], h.normal[2],
+              h.front_face, h.material, h.prim);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string scene = "cornell_box", variant, out = "image.ppm";
   int width = 0, spp = 0, depth = 0, device = 0;
@@ -180,6 +222,8 @@ int main(int argc, char** argv) {
   int frames = 0;  // 0 = one frame, written to --out itself
   double orbit = 0.0;  // degrees per frame
   bool temporal = false;
+  bool pick = false;  // one ray query through pixel (pick_x, pick_y) instead of a render
+  int pick_x = 0, pick_y = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -228,7 +272,11 @@ int main(int argc, char** argv) {
     else if (a == "--orbit") orbit = std::atof(next());
     else if (a == "--temporal") temporal = true;
     else if (a == "--out") out = next();
-    else {
+    else if (a == "--pick") {
+      pick = true;
+      pick_x = std::atoi(next());
+      pick_y = std::atoi(next());
+    } else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
     }
@@ -258,6 +306,11 @@ int main(int argc, char** argv) {
   if (rth_serialize(s, world, lights, &blob) != 0) {
     std::fprintf(stderr, "serialize: %s\n", rth_last_error());
     return 1;
+  }
+  if (pick) {
+    const int status = pick_pixel(blob, cam, pick_x, pick_y, seed, device);
+    rth_scene_free(s);
+    return status;
   }
   std::fprintf(stderr, "Rendering %s %dx%d, %d spp (requested %d), depth %d on HIP device %d\n",
                scene.c_str(), cam.image_width, cam.image_height, cam.samples_per_pixel,

@@ -519,6 +519,8 @@ int rt_scene_create(const rt_scene_blob* blob, int device, rt_scene** out) {
     sc->jit_walker = rtj::generate(F, &sc->jit_msg);
     sc->jit_state = sc->jit_walker.empty() ? -1 : 0;
   }
+  sc->prim_word = F.prim_word;  // the ray query's prim table (rt_query.hip uploads it on first use)
+  sc->prim_id = F.prim_id;
   sc->sphere_light0 = -1;
   for (size_t i = 0; i < F.light_offs.size(); ++i)
     if ((F.lights[F.light_offs[i]] & 0xffu) == RTL_SPHERE) {
@@ -540,6 +542,7 @@ void rt_scene_destroy(rt_scene* sc) {
   (void)hipDeviceSynchronize();
   for (const rtj::Kernel& k : sc->jit_k) rtj::release_kernel(k);  // the module cache's holds
   if (sc->dev) (void)hipFree(sc->dev);
+  if (sc->prim_dev) (void)hipFree(sc->prim_dev);
   for (const auto& sl : sc->slots) {
     if (sl->work) (void)hipFree(sl->work);
     if (sl->work2) (void)hipFree(sl->work2);

@@ -217,6 +217,10 @@ struct Emitter {
   std::vector<std::pair<size_t, PrimBox>> pbox;
   // transform chains longer than RTL_MAX_CHAIN (pre-relocation positions, root first)
   std::vector<std::vector<uint32_t>> long_chains;
+  // the world's leaf records (QUAD, SPHERE, VOLUME; pre-relocation position) in emission order,
+  // which is the blob's pre-order, each with the prim the reference's record carries for a hit
+  // the walker attributes to it (FlatScene::prim_word / prim_id)
+  std::vector<std::pair<size_t, uint32_t>> prims;
 
   explicit Emitter(std::vector<uint32_t>& words, int64_t nm) : w(words), n_mats(nm) {}
 
@@ -256,6 +260,7 @@ struct Emitter {
   void quad(const Node& n, bool light) {
     if (!check_mat(n.mat) && !light) return;
     size_t p = push(RTL_QUAD, light ? RTL_LQUAD_WORDS : RTL_QUAD_WORDS);
+    if (!light) prims.push_back({p, (uint32_t)prims.size()});
     const double* f = n.f;  // q 0-2, u 3-5, v 6-8, n 9-11, w 12-14, d 15, area 16
     const double u[3] = {f[3], f[4], f[5]}, v[3] = {f[6], f[7], f[8]}, wv[3] = {f[12], f[13], f[14]};
     // A = v x w, B = w x u (triple-product form of the planar coordinates, rt_layout.h)
@@ -329,6 +334,7 @@ struct Emitter {
   void sphere(const Node& n, bool light) {
     if (!check_mat(n.mat) && !light) return;
     size_t p = push(RTL_SPHERE, RTL_SPHERE_WORDS);
+    if (!light) prims.push_back({p, (uint32_t)prims.size()});
     const double* f = n.f;  // c 0-2, radius 3, cvec 4-6
     w[p + 2] = (uint32_t)(n.mat < 0 ? 0 : n.mat);
     if (n.moving) w[p] |= RTL_SPHERE_MOVING, has_moving = true;
@@ -422,11 +428,21 @@ struct Emitter {
         size_t p = push(RTL_BVH, RTL_BVH_WORDS);
         for (int k = 0; k < 6; ++k) putd(w, p, k, n.bbox[k]);
         ++bvh_depth;
+        const size_t a0 = prims.size();
         emit(*n.kids[0], frame, chain, in_volume);
         if (same_tree(*n.kids[0], *n.kids[1]) && !has_volume_node(*n.kids[1])) {
           size_t d = push(RTL_DUP, RTL_DUP_WORDS);
+          const size_t b0 = prims.size();
           emit(*n.kids[1], frame, chain, in_volume);
           set_skip(d);
+          // The walker tests the first copy only and reports its record. The reference re-tests
+          // the second over [t_min, rec.t] (hittable.rs:223-228): a quad's inclusive interval
+          // accepts again, so its record is the second copy's; a sphere's strict one does not, so
+          // it is the first's. A quad of the first copy therefore carries the second copy's prim,
+          // and the second copy's (which no product walk reports) the first's.
+          for (size_t k = 0; status == RT_OK && b0 + k < prims.size() && a0 + k < b0; ++k)
+            if ((w[prims[a0 + k].first] & 0xffu) == RTL_QUAD)
+              std::swap(prims[a0 + k].second, prims[b0 + k].second);
         } else {
           emit(*n.kids[1], frame, chain, in_volume);
         }
@@ -476,6 +492,7 @@ struct Emitter {
         has_volume = true;
         if (bvh_depth > 0) volume_in_bvh = true;
         size_t p = push(RTL_VOLUME, RTL_VOLUME_WORDS);
+        prims.push_back({p, (uint32_t)prims.size()});
         w[p + 2] = (uint32_t)n.mat;
         putd(w, p, 0, n.f[0]);
         emit(*n.kids[0], frame, chain, in_volume + 1);
@@ -788,6 +805,12 @@ int flatten(const rt_scene_blob* blob, FlatScene* out, std::string* err) {
     }
   }
   while (F.nodes.size() % 4) F.nodes.push_back(0u);
+  {  // the prim table, by relocated record word
+    std::vector<std::pair<uint32_t, uint32_t>> pm;
+    for (auto& pr : em.prims) pm.push_back({map[pr.first], pr.second});
+    std::sort(pm.begin(), pm.end());
+    for (auto& pr : pm) F.prim_word.push_back(pr.first), F.prim_id.push_back(pr.second);
+  }
   uint32_t cbvh_word0 = 0, cbvh_words = 0, cbvh_stack = 0;
   {  // ordered BVHs of the product kernels (rt_obvh.cpp), appended after the records
     std::vector<PrimBox> boxes(rec_words);

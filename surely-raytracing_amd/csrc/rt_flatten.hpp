@@ -19,6 +19,10 @@ struct FlatScene {
   std::vector<uint32_t> lights;       // node-format light records
   std::vector<uint32_t> light_offs;   // word offset of each light record
   std::vector<uint8_t> texels;
+  // the table behind rt_hit.prim (include/rt_mi355x.h): every QUAD, SPHERE and VOLUME record of the
+  // world by word offset, ascending, and the place of its primitive among the world's spheres,
+  // quads and ConstantMediums in the blob's pre-order, as the reference's hit record names it
+  std::vector<uint32_t> prim_word, prim_id;
   bool has_moving = false;            // a sphere record (world or lights) carries RTL_SPHERE_MOVING
 };
 

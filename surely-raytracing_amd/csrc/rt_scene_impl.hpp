@@ -99,6 +99,11 @@ struct rt_scene {
   const uint8_t *perlin = nullptr, *texels = nullptr;
   uint32_t o_mats = 0, o_texs = 0, o_lights = 0, o_loffs = 0, o_perl = 0;  // byte offsets in dev
   int sphere_light0 = -1;  // first SPHERE light record (TraceParams::sphere_light0)
+  // the table behind rt_hit.prim (rtf::FlatScene prim_word / prim_id), kept from the flattener;
+  // prim_dev: its device copy, n words then n prims, uploaded by the scene's first ray query
+  // (rt_query.hip, under mu) and freed by rt_scene_destroy
+  std::vector<uint32_t> prim_word, prim_id;
+  uint32_t* prim_dev = nullptr;
   static constexpr int kMaxSlots = 8;
   std::vector<std::unique_ptr<RenderSlot>> slots;  // grown on demand (RenderSlot)
   int last_slot = -1;                              // the slot of the latest render

@@ -138,6 +138,44 @@ class RtTemporalParams(C.Structure):
                 ("normal_tol", C.c_float), ("min_weight", C.c_float)]
 
 
+class RtRay(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("dir", C.c_double * 3), ("time", C.c_double),
+                ("tmin", C.c_double), ("tmax", C.c_double), ("pixel", C.c_uint32),
+                ("sample", C.c_uint32)]
+
+
+class RtHit(C.Structure):
+    _fields_ = [("t", C.c_double), ("distance", C.c_double), ("p", C.c_double * 3),
+                ("normal", C.c_double * 3), ("hit", C.c_int32), ("front_face", C.c_int32),
+                ("material", C.c_int32), ("prim", C.c_int32)]
+
+
+class RtQueryParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("flags", C.c_uint32), ("mode", C.c_uint32)]
+
+
+# ray queries (rt_query_rays*): numpy views of rt_ray / rt_hit, 80 bytes each
+RT_QUERY_OCCLUSION = 0x1  # out is one uint8 per ray: 1 hit, 0 miss, 255 invalid
+RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("time", "<f8"), ("tmin", "<f8"),
+                      ("tmax", "<f8"), ("pixel", "<u4"), ("sample", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("distance", "<f8"), ("p", "<f8", 3), ("normal", "<f8", 3),
+                      ("hit", "<i4"), ("front_face", "<i4"), ("material", "<i4"), ("prim", "<i4")])
+
+
+def make_rays(origins, dirs, time=0.0, tmin=1e-4, tmax=float("inf"), pixel=None,
+              sample=0) -> np.ndarray:
+    """A RAY_DTYPE array from (n, 3) origins and directions; the other fields broadcast. `pixel`
+    defaults to the ray's index, so every ray draws from its own random stream."""
+    o = np.asarray(origins, np.float64).reshape(-1, 3)
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"] = o
+    rays["dir"] = np.asarray(dirs, np.float64).reshape(-1, 3)
+    rays["time"], rays["tmin"], rays["tmax"] = time, tmin, tmax
+    rays["pixel"] = np.arange(len(o), dtype=np.uint32) if pixel is None else pixel
+    rays["sample"] = sample
+    return rays
+
+
 class RtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rt error {code}: {msg}")
@@ -325,6 +363,13 @@ def load_device_lib(path: Path) -> C.CDLL:
         "rt_scene_lds_check": (C.c_int, [C.POINTER(RtSceneBlob), C.c_uint32, C.c_uint32,
                                          C.c_uint64, C.POINTER(C.c_uint64), C.c_int, C.c_char_p,
                                          C.c_uint32]),
+        "rt_query_rays_device": (C.c_int, [p, C.POINTER(RtQueryParams), C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_query_rays": (C.c_int, [p, C.POINTER(RtQueryParams), C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.POINTER(RtStats)]),
+        "rt_scene_prim_map": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32), C.c_uint32,
+                                        C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -666,6 +711,33 @@ class DeviceScene:
         _check_dev(self._lib.rt_render_aov_device(self._h, C.byref(cam), C.byref(opts),
                                                   C.c_void_p(dev_ptr), C.c_void_p(stream or None),
                                                   C.byref(st) if st is not None else None))
+        return st
+
+    def query(self, rays: np.ndarray, seed: int = 1, flags: int = 0, occlusion: bool = False,
+              stats: bool = False):
+        """Synchronous rt_query_rays: the closest hit of every ray of a RAY_DTYPE array
+        (make_rays) as a HIT_DTYPE array, or with occlusion=True one uint8 per ray (1 hit, 0 miss,
+        255 invalid ray). `flags`: RT_FLAG_REFERENCE_BVH or 0. Returns the array, or (array, stats)
+        with stats=True."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(len(rays), np.uint8 if occlusion else HIT_DTYPE)
+        qp = RtQueryParams(seed, flags, RT_QUERY_OCCLUSION if occlusion else 0)
+        st = RtStats()
+        if len(rays):
+            _check_dev(self._lib.rt_query_rays(self._h, C.byref(qp), rays.ctypes.data, len(rays),
+                                               out.ctypes.data, C.byref(st)))
+        return (out, st) if stats else out
+
+    def query_device(self, rays_ptr: int, n: int, out_ptr: int, seed: int = 1, flags: int = 0,
+                     occlusion: bool = False, stream: int = 0, stats: bool = False):
+        """Asynchronous rt_query_rays_device: n rt_ray records at rays_ptr (16-byte aligned, e.g. a
+        torch tensor's data_ptr()) into n rt_hit records, or n bytes with occlusion=True, at
+        out_ptr, on `stream` (e.g. torch.cuda.current_stream().cuda_stream)."""
+        qp = RtQueryParams(seed, flags, RT_QUERY_OCCLUSION if occlusion else 0)
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_query_rays_device(
+            self._h, C.byref(qp), C.c_void_p(rays_ptr), n, C.c_void_p(out_ptr),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
 
     def jit_info(self) -> tuple[int, str]:
@@ -1051,6 +1123,19 @@ def layout_stats(blob: "Blob") -> dict:
     out = (C.c_uint32 * len(LAYOUT_STATS))()
     _check_dev(device_lib().rt_scene_layout_stats(blob.ref(), out, len(LAYOUT_STATS)))
     return dict(zip(LAYOUT_STATS, (int(v) for v in out)))
+
+
+def prim_map(blob: "Blob") -> tuple[np.ndarray, np.ndarray]:
+    """Host-only: the table behind RtHit.prim (rt_scene_prim_map) as (node_word, prim), two uint32
+    arrays: every leaf record of the flattened world by word offset, ascending, and its prim."""
+    n = C.c_uint32(0)
+    _check_dev(device_lib().rt_scene_prim_map(blob.ref(), None, None, 0, C.byref(n)))
+    word, prim = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    if n.value:
+        _check_dev(device_lib().rt_scene_prim_map(blob.ref(), word.ctypes.data_as(u32p),
+                                                  prim.ctypes.data_as(u32p), n.value, C.byref(n)))
+    return word, prim
 
 
 def lds_check(blob: "Blob", flags: int = 0, n_rays: int = 4096, seed: int = 1) -> dict:
