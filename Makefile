@@ -18,7 +18,7 @@ CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 CFLAGS_O := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function
 
 HOST_SRC := $(CSRC)/host/scene.cpp $(CSRC)/host/presets.cpp $(CSRC)/host/capi.cpp
-DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
+DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_rays.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
 DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
@@ -41,13 +41,18 @@ $(BUILD)/rt_jit_sources.inc: $(JIT_HDR) $(CSRC)/embed_sources.py
 # one object per source, so an edit of the host-side generator or flattener does not recompile
 # the kernels (rt_device.hip: every ahead-of-time template instance, ~3 minutes)
 OBJ      := $(BUILD)/obj
-DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_aov.o $(OBJ)/rt_query.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
+DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_rays.o $(OBJ)/rt_aov.o $(OBJ)/rt_query.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
 $(OBJ)/rt_device.o: $(CSRC)/rt_device.hip $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the tile-list variants of the product kernels (rt_render_tiles_device): their own object, so
 # that make -j compiles them beside rt_device.o and not after it
 $(OBJ)/rt_tiles.o: $(CSRC)/rt_tiles.hip $(DEV_HDR)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# the ray variants of the product kernels (rt_render_rays_device): their own object, as the
+# tile-list variants'
+$(OBJ)/rt_rays.o: $(CSRC)/rt_rays.hip $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # adaptive sampling: schedule, tile error and resolve kernels, the driver

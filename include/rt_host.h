@@ -101,6 +101,45 @@ int rth_write_color(const float* accum, int64_t n_pixels, double samples_per_pix
                     int use_exposure, double exposure, uint8_t* rgb8_out);
 int rth_write_ppm(const char* path, const uint8_t* rgb8, int32_t width, int32_t height);
 
+/* Host ray generator for rt_render_rays (rt_mi355x.h): the rt_ray of every pixel of a width x
+ * height frame for ONE stratum (s_i, s_j) of sqrt_spp x sqrt_spp, out[j * width + i]. Each ray
+ * carries pixel = j * width + i, sample = s_j * sqrt_spp + s_i, tmin = 1e-4, tmax = +inf, and the
+ * generator rng_seed(seed, pixel, sample) (csrc/rt_rng.h) supplies, in this order, the two jitter
+ * draws and the time draw (ray.time), as get_ray does for a camera without defocus
+ * (render.rs:218-249). Frames made here are therefore rendered with stream_skip = 3 and
+ * RT_RAYS_STREAM_TIME, one path per ray and pass, accumulating over the S * S strata.
+ * The sample's position in its pixel is (px, py) = (rs * (s_i + draw1) - 0.5, rs * (s_j + draw2) -
+ * 0.5), rs = 1 / sqrt_spp, and x = (i + 0.5 + px) / width, y = (j + 0.5 + py) / height, y down.
+ * Frame of the last three kinds: f = unit(forward), r = unit(f x up), u = r x f.
+ *   RTH_PROJ_PINHOLE   cam's own ray without its lens: get_ray restated with the same fma forms
+ *                      (origin cam->center, dir not normalised); width, height, sqrt_spp, origin,
+ *                      forward, up and fov are not read (the camera's are used).
+ *   RTH_PROJ_ORTHO     dir = f (unit); origin + (x - 0.5) * fov * width / height * r + (0.5 - y) *
+ *                      fov * u: fov is the height of the view volume in world units.
+ *   RTH_PROJ_PANORAMA  equirectangular, full sphere: lon = (x - 0.5) * 2 pi, lat = (0.5 - y) * pi,
+ *                      dir = cos(lat) * (sin(lon) * r + cos(lon) * f) + sin(lat) * u (unit length
+ *                      to rounding); the frame's centre looks along f, its top row up.
+ *   RTH_PROJ_FISHEYE   equidistant: with m = min(width, height), (nx, ny) = ((2x - 1) * width / m,
+ *                      (1 - 2y) * height / m), theta = hypot(nx, ny) * fov / 2 (fov: the full angle
+ *                      in degrees across the short side), phi = atan2(ny, nx), dir = sin(theta) *
+ *                      (cos(phi) * r + sin(phi) * u) + cos(theta) * f (unit length to rounding). A
+ *                      pixel with theta > pi lies outside the sphere: its dir is all zero, an
+ *                      invalid ray, which rt_render_rays answers with NaN.
+ * Returns 0, or -1 (rth_last_error): null arguments, sizes < 1, a stratum outside sqrt_spp, an
+ * unknown kind, a zero or non-finite frame vector, a non-positive fov where it is read. */
+#define RTH_PROJ_PINHOLE 0
+#define RTH_PROJ_ORTHO 1
+#define RTH_PROJ_PANORAMA 2
+#define RTH_PROJ_FISHEYE 3
+typedef struct rth_projection {   /* 96 bytes, no padding */
+  int32_t kind;                   /* RTH_PROJ_* */
+  int32_t width, height, sqrt_spp;
+  double origin[3], forward[3], up[3];
+  double fov;
+} rth_projection;
+int rth_projection_rays(const rth_projection* proj, const rt_camera* cam /* pinhole only */,
+                        uint64_t seed, int32_t s_i, int32_t s_j, rt_ray* out);
+
 #ifdef __cplusplus
 }
 #endif

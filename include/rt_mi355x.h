@@ -878,6 +878,75 @@ int rt_query_rays(rt_scene* scene, const rt_query_params* params, const rt_ray* 
 int rt_scene_prim_map(const rt_scene_blob* blob, uint32_t* node_word, uint32_t* prim, uint32_t cap,
                       uint32_t* n_out);
 
+/* ---- ray renders: path-traced radiance for caller-supplied rays ----------------------------------
+ * What does this ray see? rt_query_rays answers what a caller's ray hits; this entry point runs the
+ * path tracer itself on it, through the kernels of rt_render (the ahead-of-time instance of the
+ * scene's variant or its scene-specialised kernel, the same flags), so a panorama or fisheye frame,
+ * an irradiance probe, a light-map texel or one pixel's radiance for debugging come out at the
+ * parity of the pinhole render. The result is a plain n_rays*3 float buffer of sums, as rt_render's
+ * accum: the denoisers, the temporal pass and the output stage take a frame made of it unchanged.
+ *
+ * Paths and streams. Ray r runs S*S paths, S = sqrt_paths: k = s_j*S + s_i, s_j outer, s_i inner.
+ * Path k
+ *   1. seeds its generator with rng_seed(seed, ray.pixel, ray.sample + k) (the sample key mod 2^32);
+ *   2. discards stream_skip generator steps;
+ *   3. takes its time: with RT_RAYS_STREAM_TIME (needs stream_skip >= 1) the last discarded step,
+ *      read as random_double; otherwise ray.time;
+ *   4. L_k = ray_color(Ray{origin, dir, time}, max_depth) (render.rs:251-311) continues that
+ *      generator, with `background` as the miss colour.
+ * stream_skip = 3 with RT_RAYS_STREAM_TIME leaves the stream exactly where get_ray leaves it for a
+ * camera without defocus (two jitter draws, the time draw): a ray that equals a camera ray then
+ * gives that pixel-sample's value bit for bit, and a host ray generator may spend draws 1-2 on its
+ * own jitter (rt_host.h rth_projection_rays does). ray.tmin and ray.tmax are NOT read: ray_color's
+ * interval is [1e-4, inf) at every bounce, and the scene-specialised walker's is fixed.
+ *
+ * Sum. rgb[3r ..] is the sum of the L_k formed exactly as rt_render forms a pixel's sum at
+ * sqrt_spp = S: per s_j block partials of 8 consecutive s_i, the row total over the blocks, then
+ * the rows in order, in f64, rounded once to f32. Without RT_FLAG_OVERWRITE the value written is
+ * (float)((double)old + sum). A ray's result depends on that ray and the params alone: not on its
+ * place in the batch, on n_rays, or on how the call was split into launches or chunks.
+ *
+ * Invalid rays: a non-finite origin, dir or time component, or a dir that is all zero. Such a ray
+ * never hands its values to the walker (its lane walks a fixed harmless ray with its wave); its
+ * three outputs become quiet NaN whatever the flags. The other rays are unaffected and the call
+ * returns RT_OK.
+ *
+ * Checked before the scene is read and before any HIP call, RT_ERR_INVALID_ARG each: a null scene,
+ * params, rays or rgb; n_rays >= 2^31; flag bits other than RT_FLAG_OVERWRITE, RT_FLAG_INTERPRETER,
+ * RT_FLAG_REFERENCE_BVH and RT_FLAG_SEMANTICS_REFERENCE (RT_FLAG_COUNT_OPS included: the counting
+ * kernels have no ray variant); unknown mode bits; _pad0 != 0; sqrt_paths < 1; max_depth < 0;
+ * stream_skip > RT_RAYS_MAX_SKIP; RT_RAYS_STREAM_TIME with stream_skip == 0; rays not 16-byte
+ * aligned. The background is passed through as it is, non-finite values included, as the
+ * reference's. sqrt_paths > 32768 or max_depth > 0xffffff: RT_ERR_UNSUPPORTED. With
+ * RT_FLAG_SEMANTICS_REFERENCE, an empty light list and a diffuse or volume material:
+ * RT_ERR_EMPTY_LIGHTS, as a render. n_rays == 0 returns RT_OK and touches nothing. Slots, stream
+ * ordering, re-entrancy and lifetime are those of rt_render_device. rt_stats as rt_render_device
+ * fills it: samples = n_rays * S * S, launches = path-kernel launches.
+ *
+ * Not covered: second moments for ray renders, subsets of the stratum rows, rt_multi_*, op
+ * counting. */
+#define RT_RAYS_STREAM_TIME 0x1u  /* a path's time is the last skipped draw, not ray.time */
+#define RT_RAYS_MAX_SKIP 16
+
+typedef struct rt_rays_params {   /* 56 bytes, no padding */
+  uint64_t seed;
+  uint32_t flags;        /* RT_FLAG_OVERWRITE | INTERPRETER | REFERENCE_BVH | SEMANTICS_REFERENCE */
+  uint32_t mode;         /* RT_RAYS_*; unknown bits RT_ERR_INVALID_ARG */
+  int32_t  sqrt_paths;   /* S >= 1: S*S paths per ray, S <= 32768 */
+  int32_t  max_depth;    /* 0 .. 0xffffff, as rt_camera.max_depth */
+  uint32_t stream_skip;  /* generator steps discarded before a path starts, 0..RT_RAYS_MAX_SKIP */
+  uint32_t _pad0;        /* must be 0 */
+  double   background[3];
+} rt_rays_params;
+
+/* asynchronous on hip_stream (may be NULL): device buffers; stats != NULL synchronises */
+int rt_render_rays_device(rt_scene* scene, const rt_rays_params* params, const rt_ray* rays_dev,
+                          uint64_t n_rays, float* rgb_dev /* n_rays*3 */, void* hip_stream,
+                          rt_stats* stats);
+/* synchronous, host buffers */
+int rt_render_rays(rt_scene* scene, const rt_rays_params* params, const rt_ray* rays,
+                   uint64_t n_rays, float* rgb, rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,10 @@ pub const RT_TEMPORAL_VARIANCE_OF_MEAN: u32 = 0x2;
 // ray queries
 pub const RT_QUERY_OCCLUSION: u32 = 0x1;
 
+// ray renders
+pub const RT_RAYS_STREAM_TIME: u32 = 0x1;
+pub const RT_RAYS_MAX_SKIP: u32 = 16;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -251,6 +255,20 @@ pub struct rt_query_params {
     pub mode: u32,  // 0 or RT_QUERY_OCCLUSION
 }
 
+/// Parameters of rt_render_rays*; 56 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_rays_params {
+    pub seed: u64,
+    pub flags: u32,       // RT_FLAG_OVERWRITE | INTERPRETER | REFERENCE_BVH | SEMANTICS_REFERENCE
+    pub mode: u32,        // RT_RAYS_*
+    pub sqrt_paths: i32,  // S >= 1: S*S paths per ray
+    pub max_depth: i32,   // 0 .. 0xffffff
+    pub stream_skip: u32, // generator steps discarded before a path starts, 0..RT_RAYS_MAX_SKIP
+    pub _pad0: u32,       // must be 0
+    pub background: [f64; 3],
+}
+
 /// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage, rt_temporal).
 #[repr(C)]
 pub struct rt_scene {
@@ -407,4 +425,10 @@ extern "C" {
                          stats: *mut rt_stats) -> c_int;
     pub fn rt_scene_prim_map(blob: *const rt_scene_blob, node_word: *mut u32, prim: *mut u32,
                              cap: u32, n_out: *mut u32) -> c_int;
+    pub fn rt_render_rays_device(scene: *mut rt_scene, params: *const rt_rays_params,
+                                 rays_dev: *const rt_ray, n_rays: u64, rgb_dev: *mut f32,
+                                 hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_render_rays(scene: *mut rt_scene, params: *const rt_rays_params,
+                          rays: *const rt_ray, n_rays: u64, rgb: *mut f32,
+                          stats: *mut rt_stats) -> c_int;
 }

@@ -236,6 +236,128 @@ int rth_camera_orbit_y(const rt_camera* in, const double pivot[3], double degree
   return 0;
 }
 
+// ---- rth_projection_rays: host ray generator for rt_render_rays
+namespace {
+// csrc/rt_rng.h restated for the host (rng_seed: pcg2d key; rng_step: xoroshiro64*);
+// tests/test_rays_host.py pins the draws to the oracle's camera ray bit for bit
+struct HostRng {
+  uint32_t s0, s1;
+};
+uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
+HostRng host_rng_seed(uint64_t seed, uint32_t pixel, uint32_t sample) {
+  const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+  const uint32_t k0 = (lo ^ 0x85EBCA6Bu) * 0x9E3779B9u + 1013904223u;
+  const uint32_t k1 = (hi ^ 0xC2B2AE35u) * 0x9E3779B9u + (k0 ^ 0x27D4EB2Fu);
+  uint32_t v0 = pixel * 1664525u + k0, v1 = sample * 1664525u + k1;
+  for (int r = 0; r < 2; ++r) {
+    v0 += v1 * 1664525u;
+    v1 += v0 * 1664525u;
+    v0 ^= v0 >> 16;
+    v1 ^= v1 >> 16;
+  }
+  if ((v0 | v1) == 0u) v0 = 0x9E3779B9u;
+  return {v0, v1};
+}
+double host_rnd(HostRng& g) {
+  const uint32_t s0 = g.s0;
+  uint32_t s1 = g.s1;
+  const uint32_t result = s0 * 0x9E3779BBu;
+  s1 ^= s0;
+  g.s0 = rotl32(s0, 26) ^ s1 ^ (s1 << 9);
+  g.s1 = rotl32(s1, 13);
+  return (double)result * 0x1p-32;
+}
+bool unit3(const double* v, double* out) {
+  const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  if (!(n > 0.0) || !std::isfinite(n)) return false;
+  for (int k = 0; k < 3; ++k) out[k] = v[k] / n;
+  return true;
+}
+void cross3(const double* a, const double* b, double* o) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+}  // namespace
+
+int rth_projection_rays(const rth_projection* pr, const rt_camera* cam, uint64_t seed, int32_t s_i,
+                        int32_t s_j, rt_ray* out) {
+  if (!pr || !out) return fail("projection_rays: null argument");
+  const bool pin = pr->kind == RTH_PROJ_PINHOLE;
+  if (pr->kind < RTH_PROJ_PINHOLE || pr->kind > RTH_PROJ_FISHEYE) return fail("projection_rays: unknown kind");
+  if (pin && !cam) return fail("projection_rays: the pinhole projection needs a camera");
+  const int W = pin ? cam->image_width : pr->width, H = pin ? cam->image_height : pr->height;
+  const int S = pin ? cam->sqrt_spp : pr->sqrt_spp;
+  if (W < 1 || H < 1 || S < 1 || (int64_t)W * H >= (1ll << 31))
+    return fail("projection_rays: width, height and sqrt_spp must be >= 1 (and width * height < 2^31)");
+  if (s_i < 0 || s_i >= S || s_j < 0 || s_j >= S) return fail("projection_rays: stratum outside sqrt_spp");
+  double f[3] = {0, 0, 0}, r[3] = {0, 0, 0}, u[3] = {0, 0, 0};
+  if (!pin) {
+    double fxu[3];
+    if (!unit3(pr->forward, f)) return fail("projection_rays: forward is zero or not finite");
+    cross3(f, pr->up, fxu);
+    if (!unit3(fxu, r)) return fail("projection_rays: up is zero, not finite or parallel to forward");
+    cross3(r, f, u);
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(pr->origin[k])) return fail("projection_rays: origin is not finite");
+    if (pr->kind != RTH_PROJ_PANORAMA && !(pr->fov > 0.0 && std::isfinite(pr->fov)))
+      return fail("projection_rays: fov must be positive and finite");
+  }
+  // recip_sqrt_spp as Camera::new forms it (render.rs:76); the pinhole takes the camera's own
+  const double rs = pin ? cam->recip_sqrt_spp : 1.0 / (double)S;
+  for (int j = 0; j < H; ++j) {
+    for (int i = 0; i < W; ++i) {
+      rt_ray& q = out[(size_t)j * W + i];
+      q.pixel = (uint32_t)(j * W + i);
+      q.sample = (uint32_t)(s_j * S + s_i);
+      HostRng g = host_rng_seed(seed, q.pixel, q.sample);
+      const double px = std::fma(rs, (double)s_i + host_rnd(g), -0.5);
+      const double py = std::fma(rs, (double)s_j + host_rnd(g), -0.5);
+      q.time = host_rnd(g);
+      q.tmin = 1e-4;
+      q.tmax = INFINITY;
+      if (pin) {  // get_ray (render.rs:218-249) without the defocus disk, the device's fma forms
+        for (int k = 0; k < 3; ++k) {
+          const double pc = std::fma((double)j, cam->pixel_delta_v[k],
+                                     std::fma((double)i, cam->pixel_delta_u[k], cam->pixel00_loc[k]));
+          const double ps = pc + std::fma(px, cam->pixel_delta_u[k], cam->pixel_delta_v[k] * py);
+          q.origin[k] = cam->center[k];
+          q.dir[k] = ps - cam->center[k];
+        }
+        continue;
+      }
+      const double x = ((double)i + 0.5 + px) / (double)W, y = ((double)j + 0.5 + py) / (double)H;
+      double a = 0.0, b = 0.0, c = 0.0;  // dir = a r + b u + c f
+      double oa = 0.0, ob = 0.0;         // origin offset along r and u
+      if (pr->kind == RTH_PROJ_ORTHO) {
+        c = 1.0;
+        oa = (x - 0.5) * pr->fov * (double)W / (double)H;
+        ob = (0.5 - y) * pr->fov;
+      } else if (pr->kind == RTH_PROJ_PANORAMA) {
+        const double lon = (x - 0.5) * 2.0 * M_PI, lat = (0.5 - y) * M_PI;
+        a = std::cos(lat) * std::sin(lon);
+        b = std::sin(lat);
+        c = std::cos(lat) * std::cos(lon);
+      } else {
+        const double m = (double)(W < H ? W : H);
+        const double nx = (2.0 * x - 1.0) * (double)W / m, ny = (1.0 - 2.0 * y) * (double)H / m;
+        const double th = std::hypot(nx, ny) * (pr->fov * M_PI / 180.0) * 0.5;
+        if (th <= M_PI) {
+          const double ph = std::atan2(ny, nx);
+          a = std::sin(th) * std::cos(ph);
+          b = std::sin(th) * std::sin(ph);
+          c = std::cos(th);
+        }
+      }
+      for (int k = 0; k < 3; ++k) {
+        q.origin[k] = pr->origin[k] + oa * r[k] + ob * u[k];
+        q.dir[k] = a * r[k] + b * u[k] + c * f[k];
+      }
+    }
+  }
+  return 0;
+}
+
 int rth_preset(rth_scene* s, const char* name, const char* variant, int32_t width, int32_t spp,
                int32_t depth, double aspect, int32_t* world_out, int32_t* lights_out,
                rt_camera* cam_out) {

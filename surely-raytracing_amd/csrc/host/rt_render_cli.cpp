@@ -17,13 +17,18 @@
 //      and is written to NAME_%03d.ppm
 //   -> with --pick X Y: no render; rt_query_rays with the pixel-centre ray of the preset's camera,
 //      `hit t distance p normal front material prim` on one line of stdout
+//   -> with --projection ortho|panorama|fisheye [--fov F]: the frame's rays come from
+//      rth_projection_rays (eye, view direction and up of the preset's camera) and are path traced
+//      by rt_render_rays, S * S passes of one path per ray accumulated without RT_FLAG_OVERWRITE;
+//      the output options apply to the frame as to any other (the denoisers, --adaptive, --frames
+//      and --pick need the pinhole camera's AOVs or tiles and do not combine)
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
 //                      [--reference-semantics] [--auto-exposure] [--denoise [levels]]
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
 //                      [--device-output] [--frames N] [--orbit DEG] [--temporal] [--out file.ppm]
-//                      [--pick X Y]
+//                      [--pick X Y] [--projection ortho|panorama|fisheye] [--fov F]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -207,6 +212,64 @@ static int pick_pixel(const rt_scene_blob& blob, const rt_camera& cam, int x, in
   return 0;
 }
 
+// --projection: the preset's eye and view frame, another projection. fov <= 0: the height of the
+// pinhole's viewport for ortho, 180 degrees for fisheye. Pixels whose ray is invalid (a fisheye
+// pixel outside the sphere) come back NaN and are written black.
+static int render_projection(const rt_scene_blob& blob, const rt_camera& cam, int kind, double fov,
+                             uint64_t seed, uint32_t flags, int device, std::vector<float>& accum,
+                             rt_stats* total) {
+  const int W = cam.image_width, H = cam.image_height, S = cam.sqrt_spp;
+  rth_projection pr;
+  std::memset(&pr, 0, sizeof(pr));
+  pr.kind = kind;
+  pr.width = W;
+  pr.height = H;
+  pr.sqrt_spp = S;
+  double vh = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    pr.origin[k] = cam.center[k];
+    pr.forward[k] = cam.pixel00_loc[k] + 0.5 * (W - 1) * cam.pixel_delta_u[k] +
+                    0.5 * (H - 1) * cam.pixel_delta_v[k] - cam.center[k];
+    pr.up[k] = -cam.pixel_delta_v[k];
+    vh += cam.pixel_delta_v[k] * cam.pixel_delta_v[k];
+  }
+  pr.fov = fov > 0.0 ? fov : (kind == RTH_PROJ_ORTHO ? std::sqrt(vh) * H : 180.0);
+  rt_rays_params rp;
+  std::memset(&rp, 0, sizeof(rp));
+  rp.seed = seed;
+  rp.mode = RT_RAYS_STREAM_TIME;
+  rp.sqrt_paths = 1;
+  rp.max_depth = cam.max_depth;
+  rp.stream_skip = 3;  // the generator's two jitter draws and its time draw
+  for (int k = 0; k < 3; ++k) rp.background[k] = cam.background[k];
+  std::vector<rt_ray> rays((size_t)W * H);  // operator new: 16-byte aligned
+  rt_scene* sc = nullptr;
+  int rc = rt_scene_create(&blob, device, &sc);
+  std::memset(total, 0, sizeof(*total));
+  for (int s_j = 0; rc == RT_OK && s_j < S; ++s_j)
+    for (int s_i = 0; rc == RT_OK && s_i < S; ++s_i) {
+      if (rth_projection_rays(&pr, nullptr, seed, s_i, s_j, rays.data()) != 0) {
+        std::fprintf(stderr, "projection: %s\n", rth_last_error());
+        rt_scene_destroy(sc);
+        return 1;
+      }
+      rp.flags = (flags & ~RT_FLAG_OVERWRITE) | (s_i + s_j == 0 ? RT_FLAG_OVERWRITE : 0u);
+      rt_stats st;
+      rc = rt_render_rays(sc, &rp, rays.data(), rays.size(), accum.data(), &st);
+      total->ms_kernel += st.ms_kernel;
+      total->samples += st.samples;
+      total->launches += st.launches;
+    }
+  rt_scene_destroy(sc);
+  if (rc != RT_OK) {
+    std::fprintf(stderr, "rt_render_rays: %d %s\n", rc, rt_last_error());
+    return 1;
+  }
+  for (float& v : accum)
+    if (v != v) v = 0.f;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::string scene = "cornell_box", variant, out = "image.ppm";
   int width = 0, spp = 0, depth = 0, device = 0;
@@ -224,6 +287,8 @@ int main(int argc, char** argv) {
   bool temporal = false;
   bool pick = false;  // one ray query through pixel (pick_x, pick_y) instead of a render
   int pick_x = 0, pick_y = 0;
+  int projection = RTH_PROJ_PINHOLE;  // another one: the frame through rt_render_rays
+  double fov = 0.0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -276,7 +341,16 @@ int main(int argc, char** argv) {
       pick = true;
       pick_x = std::atoi(next());
       pick_y = std::atoi(next());
-    } else {
+    } else if (a == "--projection") {
+      const std::string v = next();
+      projection = v == "ortho" ? RTH_PROJ_ORTHO : v == "panorama" ? RTH_PROJ_PANORAMA
+                   : v == "fisheye" ? RTH_PROJ_FISHEYE : -1;
+      if (projection < 0) {
+        std::fprintf(stderr, "--projection %s: ortho, panorama or fisheye\n", v.c_str());
+        return 2;
+      }
+    } else if (a == "--fov") fov = std::atof(next());
+    else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
     }
@@ -292,6 +366,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr,
                  "--orbit and --temporal need --frames N (N >= 1); --frames does not combine with "
                  "--adaptive (rt_temporal takes one sample count for the whole frame)\n");
+    return 2;
+  }
+  if (projection != RTH_PROJ_PINHOLE && (denoise_levels || adaptive || frames || pick)) {
+    std::fprintf(stderr,
+                 "--projection does not combine with --denoise, --denoise-var, --adaptive, --frames "
+                 "or --pick: they take the pinhole camera's AOVs, tiles or pixels\n");
     return 2;
   }
   rth_scene* s = rth_scene_new(build_seed);
@@ -339,7 +419,10 @@ int main(int argc, char** argv) {
   std::vector<float> accum((size_t)cam.image_width * cam.image_height * 3, 0.f);
   rt_stats st;
   int rc;
-  if (adaptive) {
+  if (projection != RTH_PROJ_PINHOLE) {
+    if (render_projection(blob, cam, projection, fov, seed, o.flags, device, accum, &st) != 0)
+      return 1;
+  } else if (adaptive) {
     // the adaptive driver; with --denoise the plain filter over its resolved frame
     rt_scene* sc = nullptr;
     rt_adaptive* ad = nullptr;

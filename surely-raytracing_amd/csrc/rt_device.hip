@@ -97,19 +97,29 @@ struct MomentsOut<true> {
 // list's length, the pixel position comes from the listed tile, and the pairs (q0 = entry * n_sj)
 // and the chunks' carries (64 pixels per entry) stay compact, indexed by the position in the list.
 // The plain instantiation (TileIn<false>, an empty argument) names none of it.
-template <bool TILES>
+// RAYS (rt_render_rays_device): the launch's "image" is the batch, 8 rays wide, so tile t is rays
+// 64 t .. 64 t + 63 and the pixel index is the ray index; lanes past n_rays leave, and an invalid
+// ray's three outputs become quiet NaN whatever the mode (the validity test of trace_body's ray
+// block, on the same words).
+template <int LK>
 struct TileIn {};
 template <>
-struct TileIn<true> {
+struct TileIn<kLaunchTiles> {
   const uint32_t* list;
 };
-template <bool M2, bool TILES = false>
+template <>
+struct TileIn<kLaunchRays> {
+  const uint4* rays;
+  uint32_t n_rays;
+};
+template <bool M2, int LK = kLaunchPlain>
 __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part,
                                                  double* __restrict__ tot,
                                                  float* __restrict__ accum, int W, int n_rows,
                                                  int tiles_x, int n_tiles, int n_sj, int S,
                                                  int n_pairs_r, int n_pairs_a, int mode,
-                                                 MomentsOut<M2> mo, TileIn<TILES> ti = {}) {
+                                                 MomentsOut<M2> mo, TileIn<LK> ti = {}) {
+  constexpr bool TILES = LK == kLaunchTiles, RAYS = LK == kLaunchRays;
   const int tile_id = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   const int pv = threadIdx.x & 63;
   if (tile_id >= n_tiles) return;
@@ -119,6 +129,9 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
   const int tile_w = min(kWaveTile, W - tx * kWaveTile);
   const int tile_h = min(kWaveTile, n_rows - ty * kWaveTile);
   if (pv >= tile_w * tile_h) return;
+  if constexpr (RAYS) {
+    if ((uint32_t)tile_id * 64u + (uint32_t)pv >= ti.n_rays) return;
+  }
   const int x = tx * kWaveTile + pv % tile_w, kr = ty * kWaveTile + pv / tile_w;
   const size_t i = (size_t)kr * W + x;
   const size_t ic = TILES ? (size_t)tile_id * 64 + pv : i;  // the pixel's carry between chunks
@@ -222,6 +235,19 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
     if (M2) m0 = fma(R0, R0, m0), m1 = fma(R1, R1, m1), m2c = fma(R2, R2, m2c);
   }
   float* a = accum + 3 * i;
+  if constexpr (RAYS) {
+    if (mode & 2) {
+      const uint4* R = ti.rays + i * 5u;
+      const uint4 r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3];
+      const bool dir0 = ((r1.z | r2.x | r2.z) == 0u) & (((r1.w | r2.y | r2.w) & 0x7fffffffu) == 0u);
+      const bool valid = finite_hi(r0.y) && finite_hi(r0.w) && finite_hi(r1.y) && finite_hi(r1.w) &&
+                         finite_hi(r2.y) && finite_hi(r2.w) && finite_hi(r3.y) && !dir0;
+      if (!valid) {
+        a[0] = a[1] = a[2] = __uint_as_float(0x7fc00000u);
+        return;
+      }
+    }
+  }
   if (mode & 2) {
     if (mode & 4) {
       a[0] = (float)t0, a[1] = (float)t1, a[2] = (float)t2;
@@ -577,7 +603,7 @@ int rt_jit_check(const rt_scene_blob* blob, const char* arch, int* state, char* 
     std::string log;
     // the variant of a product render whose plan stages the scene's tables
     const rtv::Variant v = rtv::choose_variant(F.hdr, 0u, true);
-    rc = rtj::compile(rtj::kernel_source(walker, v, false), arch, &code, &log);
+    rc = rtj::compile(rtj::kernel_source(walker, v, kLaunchPlain), arch, &code, &log);
     if (rc != 0) {
       *state = -2;
       out = log;
@@ -586,10 +612,23 @@ int rt_jit_check(const rt_scene_blob* blob, const char* arch, int* state, char* 
     // too, so that the code-object cache holds both; the returned source is the plain walker's
     const char* tv = std::getenv("RT_JIT_CHECK_TILES");
     if (rc == 0 && tv && std::strcmp(tv, "1") == 0) {
-      rc = rtj::compile(rtj::kernel_source(walker, v, true), arch, &code, &log);
+      rc = rtj::compile(rtj::kernel_source(walker, v, kLaunchTiles), arch, &code, &log);
       if (rc != 0) {
         *state = -2;
         out = log;
+      }
+    }
+    // RT_JIT_CHECK_RAYS=1: the ray variant (rt_render_rays_device) as well; the returned source is
+    // then that kernel's whole translation unit, the walker and the wrapper that names the instance
+    const char* rv = std::getenv("RT_JIT_CHECK_RAYS");
+    if (rc == 0 && rv && std::strcmp(rv, "1") == 0) {
+      const std::string src = rtj::kernel_source(walker, v, kLaunchRays);
+      rc = rtj::compile(src, arch, &code, &log);
+      if (rc != 0) {
+        *state = -2;
+        out = log;
+      } else {
+        out = src;
       }
     }
   }
@@ -820,6 +859,12 @@ struct TileJob {
   int sj_step;
   uint64_t n_px;
 };
+// A ray render's batch (rt_render_rays_device), its arguments checked by the entry point
+struct RayJob {
+  const rt_ray* rays;  // device
+  uint64_t n_rays;
+  uint32_t skip, mode;
+};
 
 namespace {
 
@@ -830,18 +875,21 @@ struct PathKernel {
   kern_t kern = nullptr;
   hipFunction_t jfn = nullptr;  // runs instead of kern when set
 };
-int select_kernel(rt_scene* sc, uint32_t flags, const LdsPlan& LP, bool tiles, bool want_jit,
+int select_kernel(rt_scene* sc, uint32_t flags, const LdsPlan& LP, int launch, bool want_jit,
                   PathKernel* out) {
   const rtv::Variant v = rtv::choose_variant(sc->hdr, flags, LP.stage_scene != 0);
-  out->kern = tiles ? tile_trace_kernel(v) : trace_kernel(v, (flags & RT_FLAG_COUNT_OPS) != 0);
+  out->kern = launch == kLaunchTiles  ? tile_trace_kernel(v)
+              : launch == kLaunchRays ? ray_trace_kernel(v)
+                                      : trace_kernel(v, (flags & RT_FLAG_COUNT_OPS) != 0);
   if (!out->kern)
-    return set_err(RT_ERR_INVALID_ARG, tiles ? "no tile-list variant of this kernel"
-                                             : "no ahead-of-time kernel of this variant");
+    return set_err(RT_ERR_INVALID_ARG, launch == kLaunchTiles  ? "no tile-list variant of this kernel"
+                                       : launch == kLaunchRays ? "no ray variant of this kernel"
+                                                               : "no ahead-of-time kernel of this variant");
   if (!want_jit || LP.lds_bytes + LP.static_lds > sc->lds_module_max) return RT_OK;
-  rtj::Kernel& jk = sc->jit_k[tiles ? 1 : 0];
+  rtj::Kernel& jk = sc->jit_k[launch];
   if (!jk.fn) {
     std::string log;
-    if (rtj::get_kernel(sc->jit_walker, sc->device, v, tiles, &jk, &log) != 0) {
+    if (rtj::get_kernel(sc->jit_walker, sc->device, v, launch, &jk, &log) != 0) {
       sc->jit_state = -2;
       sc->jit_msg = log;
     } else {
@@ -986,16 +1034,17 @@ int grow_slot(RenderSlot* sl, const WorkPlan& wp, bool m2_chunked, const TileJob
   return RT_OK;
 }
 
-// One rt_reduce launch over (M2, TILES), with the instance's own MomentsOut / TileIn arguments,
-// of the chunk P describes; the carries live in the slot (tot2: only between chunks)
-template <bool M2, bool TILES>
+// One rt_reduce launch over (M2, launch kind), with the instance's own MomentsOut / TileIn
+// arguments, of the chunk P describes; the carries live in the slot (tot2: only between chunks)
+template <bool M2, int LK>
 void launch_reduce(const TraceParams& P, RenderSlot* sl, float* accum, float* m2, int n_tiles,
                    int mode, hipStream_t stream) {
   MomentsOut<M2> mo;
   if constexpr (M2) mo = {(double*)sl->work2, m2};
-  TileIn<TILES> ti;
-  if constexpr (TILES) ti = {sl->tiles};
-  hipLaunchKernelGGL((rt_reduce<M2, TILES>), dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0,
+  TileIn<LK> ti;
+  if constexpr (LK == kLaunchTiles) ti = {sl->tiles};
+  if constexpr (LK == kLaunchRays) ti = {P.rays, P.n_rays};
+  hipLaunchKernelGGL((rt_reduce<M2, LK>), dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0,
                      stream, P.part, (double*)sl->work, accum, P.W, P.n_rows, P.tiles_x, n_tiles,
                      P.n_sj, P.sqrt_spp, P.n_pairs_r, P.n_pairs_a, mode, mo, ti);
 }
@@ -1004,12 +1053,14 @@ void launch_reduce(const TraceParams& P, RenderSlot* sl, float* accum, float* m2
 // kernel over the chunk's pools and one rt_reduce into the carries or, last, the accumulator.
 int launch_chunks(rt_scene* sc, RenderSlot* sl, const PathKernel& K, TraceParams& P,
                   const LdsPlan& LP, const WorkIn& in, const WorkPlan& wp, int64_t max_blocks,
-                  int sj0, uint32_t flags, float* accum, float* m2, bool tiles,
+                  int sj0, uint32_t flags, float* accum, float* m2, int launch,
                   hipStream_t stream, rt_stats* counts) {
-  static void (*const reduce[2][2])(const TraceParams&, RenderSlot*, float*, float*, int, int,
+  // (ray renders have no moments: the entry point passes no second buffer)
+  static void (*const reduce[2][3])(const TraceParams&, RenderSlot*, float*, float*, int, int,
                                     hipStream_t) = {
-      {launch_reduce<false, false>, launch_reduce<false, true>},
-      {launch_reduce<true, false>, launch_reduce<true, true>}};
+      {launch_reduce<false, kLaunchPlain>, launch_reduce<false, kLaunchTiles>,
+       launch_reduce<false, kLaunchRays>},
+      {launch_reduce<true, kLaunchPlain>, launch_reduce<true, kLaunchTiles>, nullptr}};
   const int block = LP.block;
   for (int k0 = 0; k0 < in.n_sj; k0 += wp.chunk) {
     const int cn = std::min(wp.chunk, in.n_sj - k0);
@@ -1039,7 +1090,7 @@ int launch_chunks(rt_scene* sc, RenderSlot* sl, const PathKernel& K, TraceParams
     ++sc->n_tev;
     const int mode =
         (k0 == 0 ? 1 : 0) | (k0 + cn == in.n_sj ? 2 : 0) | ((flags & RT_FLAG_OVERWRITE) ? 4 : 0);
-    reduce[m2 != nullptr][tiles](P, sl, accum, m2, in.n_tiles, mode, stream);
+    reduce[m2 != nullptr][launch](P, sl, accum, m2, in.n_tiles, mode, stream);
     HIP_TRY(hipGetLastError());
   }
   return RT_OK;
@@ -1051,13 +1102,17 @@ int launch_chunks(rt_scene* sc, RenderSlot* sl, const PathKernel& K, TraceParams
 // moments of the row totals; every other step is the plain render's. tj != nullptr: a tile-list
 // render (rt_render_tiles_device): the launch's pairs run over the list's entries and the strided
 // stratum rows sj_begin + k * sj_step, through the TILES variants of the same kernels; LDS plan,
-// kernel choice, slot, chunking and stats are shared.
+// kernel choice, slot, chunking and stats are shared. rj != nullptr: a ray render
+// (rt_render_rays_device): cam and opts describe the batch as an image 8 pixels wide and
+// ceil(n_rays / 8) rows tall (no 32760-row sub-calls: a ray item's key is the ray index, not x and
+// row), every stratum row of it, through the RAYS variants; accum is the caller's n_rays * 3 floats.
 static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_render_opts* opts,
                               float* accum, float* m2, const TileJob* tj, void* stream_v,
-                              rt_stats* stats) {
+                              rt_stats* stats, const RayJob* rj = nullptr) {
   auto t0 = std::chrono::steady_clock::now();
-  int sj0 = 0, n_sj = 0;
-  RT_TRY(check_render_args(cam, opts, true, tj ? tj->sj_step : 1, &sj0, &n_sj));
+  const int launch = rj ? kLaunchRays : tj ? kLaunchTiles : kLaunchPlain;
+  int sj0 = 0, n_sj = cam->sqrt_spp;
+  if (!rj) RT_TRY(check_render_args(cam, opts, true, tj ? tj->sj_step : 1, &sj0, &n_sj));
   if (sc->hdr.n_lights == 0 && (opts->flags & RT_FLAG_SEMANTICS_REFERENCE) && sc->hdr.pdf_materials)
     return set_err(RT_ERR_EMPTY_LIGHTS,
                    "empty light list with a diffuse/volume material: the reference panics "
@@ -1066,7 +1121,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   hipStream_t stream = (hipStream_t)stream_v;
   HIP_TRY(hipSetDevice(sc->device));
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  const size_t n_px = (size_t)opts->n_rows * cam->image_width;
+  const size_t n_px = rj ? (size_t)rj->n_rays : (size_t)opts->n_rows * cam->image_width;
   if (n_px == 0) return RT_OK;
   SlotHold hold{sc, lock};
   RT_TRY(acquire_slot(sc, lock, stream, &hold.sl));
@@ -1084,8 +1139,14 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   P.ops = sl->ops;
   P.queue = sl->queue;
   if (tj) P.sj_step = tj->sj_step;
+  if (rj) {
+    P.rays = reinterpret_cast<const uint4*>(rj->rays);
+    P.n_rays = (uint32_t)rj->n_rays;
+    P.rays_skip = rj->skip;
+    P.rays_mode = rj->mode;
+  }
   PathKernel K;
-  RT_TRY(select_kernel(sc, opts->flags, LP, tj != nullptr, want_jit, &K));
+  RT_TRY(select_kernel(sc, opts->flags, LP, launch, want_jit, &K));
   // (module kernels take their dynamic LDS size at launch)
   if (!K.jfn && LP.lds_bytes > (64u << 10))
     HIP_TRY(hipFuncSetAttribute((const void*)K.kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1096,8 +1157,9 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   const int64_t max_blocks = (int64_t)resident * std::max(1, sc->n_cu);
   // the launch's tiles: the call's whole grid, or the entries of the list
   const int n_tiles = tj ? (int)tj->n_list : P.tiles_x * ((opts->n_rows + kWaveTile - 1) / kWaveTile);
+  // (a ray batch: tiles_x = 1, so ceil(n_rays / 64) tiles, carried as whole tiles)
   const WorkIn in{n_tiles, n_sj, cam->sqrt_spp, P.n_blk, max_blocks * (LP.block / 64),
-                  !sc->hdr.has_bvh || LP.row_lds_off != ~0u, tj ? (size_t)n_tiles * 64 : n_px,
+                  !sc->hdr.has_bvh || LP.row_lds_off != ~0u, tj || rj ? (size_t)n_tiles * 64 : n_px,
                   sc->mem_total, std::getenv("RT_SEG_PAIRS"), std::getenv("RT_TAIL_PAIRS"),
                   std::getenv("RT_WORKSPACE_MB")};
   const WorkPlan wp = plan_workspace(in);
@@ -1120,7 +1182,7 @@ static int render_device_rows(rt_scene* sc, const rt_camera* cam, const rt_rende
   rt_stats counts{};
   counts.samples = (uint64_t)(tj ? tj->n_px : n_px) * (uint64_t)n_sj * (uint64_t)cam->sqrt_spp;
   RT_TRY(launch_chunks(sc, sl, K, P, LP, in, wp, max_blocks, sj0, opts->flags, accum, m2,
-                       tj != nullptr, stream, &counts));
+                       launch, stream, &counts));
   ++sc->n_render;
   return complete_render(hold, stream, stats, counts, ops_buf, t0);
 }
@@ -1200,6 +1262,83 @@ int rt_render_tiles_device(rt_scene* sc, const rt_camera* cam, const rt_render_o
   }
   const TileJob tj{tiles, n_list, (int)sj_step, n_px};
   return render_device_rows(sc, cam, opts, accum, m2, &tj, stream_v, stats);
+}
+
+// made before the scene is read and before any HIP call
+static int check_rays_args(const rt_scene* sc, const rt_rays_params* rp, const rt_ray* rays,
+                           uint64_t n_rays, const float* rgb) {
+  if (!sc || !rp || !rays || !rgb) return set_err(RT_ERR_INVALID_ARG, "null argument");
+  if (n_rays >= (1ull << 31)) return set_err(RT_ERR_INVALID_ARG, "n_rays >= 2^31");
+  if (rp->flags & ~(RT_FLAG_OVERWRITE | RT_FLAG_INTERPRETER | RT_FLAG_REFERENCE_BVH |
+                    RT_FLAG_SEMANTICS_REFERENCE))
+    return set_err(RT_ERR_INVALID_ARG,
+                   "ray renders take RT_FLAG_OVERWRITE, INTERPRETER, REFERENCE_BVH and "
+                   "SEMANTICS_REFERENCE only (the counting kernels have no ray variant)");
+  if (rp->mode & ~RT_RAYS_STREAM_TIME) return set_err(RT_ERR_INVALID_ARG, "unknown ray-render mode bits");
+  if (rp->_pad0 != 0u) return set_err(RT_ERR_INVALID_ARG, "rt_rays_params._pad0 must be 0");
+  if (rp->sqrt_paths < 1 || rp->max_depth < 0)
+    return set_err(RT_ERR_INVALID_ARG, "sqrt_paths < 1 or max_depth < 0");
+  if (rp->stream_skip > RT_RAYS_MAX_SKIP)
+    return set_err(RT_ERR_INVALID_ARG, "stream_skip > RT_RAYS_MAX_SKIP");
+  if ((rp->mode & RT_RAYS_STREAM_TIME) && rp->stream_skip == 0u)
+    return set_err(RT_ERR_INVALID_ARG, "RT_RAYS_STREAM_TIME needs stream_skip >= 1");
+  if ((uintptr_t)rays % 16u) return set_err(RT_ERR_INVALID_ARG, "rays not 16-byte aligned");
+  if (rp->sqrt_paths > 32768 || rp->max_depth > 0xffffff)
+    return set_err(RT_ERR_UNSUPPORTED, "sqrt_paths > 32768 or max_depth > 0xffffff");
+  return RT_OK;
+}
+
+int rt_render_rays_device(rt_scene* sc, const rt_rays_params* rp, const rt_ray* rays,
+                          uint64_t n_rays, float* rgb, void* stream_v, rt_stats* stats) {
+  RT_TRY(check_rays_args(sc, rp, rays, n_rays, rgb));
+  if (n_rays == 0) return RT_OK;
+  // the batch as an image 8 pixels wide (render_device_rows): no camera geometry is read
+  rt_camera cam{};
+  cam.image_width = kWaveTile;
+  cam.image_height = (int32_t)((n_rays + kWaveTile - 1) / kWaveTile);
+  cam.sqrt_spp = rp->sqrt_paths;
+  cam.samples_per_pixel = rp->sqrt_paths * rp->sqrt_paths;
+  cam.recip_sqrt_spp = 1.0 / (double)rp->sqrt_paths;
+  cam.max_depth = rp->max_depth;
+  for (int k = 0; k < 3; ++k) cam.background[k] = rp->background[k];
+  rt_render_opts opts{};
+  opts.seed = rp->seed;
+  opts.flags = rp->flags;
+  opts.row_step = 1;
+  opts.n_rows = cam.image_height;
+  const RayJob rj{rays, n_rays, rp->stream_skip, rp->mode};
+  return render_device_rows(sc, &cam, &opts, rgb, nullptr, nullptr, stream_v, stats, &rj);
+}
+
+int rt_render_rays(rt_scene* sc, const rt_rays_params* rp, const rt_ray* rays, uint64_t n_rays,
+                   float* rgb, rt_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  RT_TRY(check_rays_args(sc, rp, rays, n_rays, rgb));
+  if (n_rays == 0) return RT_OK;
+  const size_t in_bytes = (size_t)n_rays * sizeof(rt_ray), ob = (size_t)n_rays * 3 * sizeof(float);
+  HIP_TRY(hipSetDevice(sc->device));
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc(&d_in, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_out, ob);
+  if (e == hipSuccess) e = hipMemcpy(d_in, rays, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !(rp->flags & RT_FLAG_OVERWRITE))
+    e = hipMemcpy(d_out, rgb, ob, hipMemcpyHostToDevice);
+  int rc = e == hipSuccess ? RT_OK
+                           : set_err(RT_ERR_HIP, std::string("upload rays: ") + hipGetErrorString(e));
+  rt_stats local;
+  if (rc == RT_OK)
+    rc = rt_render_rays_device(sc, rp, (const rt_ray*)d_in, n_rays, (float*)d_out, nullptr,
+                               stats ? stats : &local);
+  if (rc == RT_OK) {
+    e = hipMemcpy(rgb, d_out, ob, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download rgb: ") + hipGetErrorString(e));
+  }
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  if (rc == RT_OK && stats)
+    stats->ms_total =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
 }
 
 // Profiling builds (-DRT_PROF, not shipped): the ordered-BVH walk counters of the last render

@@ -688,7 +688,7 @@ std::string generate(const rtf::FlatScene& F, std::string* why) {
   return generate_walker(F, nullptr, why);
 }
 
-std::string kernel_source(const std::string& walker, const rtv::Variant& f, bool tiles) {
+std::string kernel_source(const std::string& walker, const rtv::Variant& f, int launch) {
   auto b = [](bool v) { return v ? "true" : "false"; };
   std::ostringstream src;
   src << "#include \"rt_kernel.h\"\nnamespace rtk {\n"
@@ -699,9 +699,9 @@ std::string kernel_source(const std::string& walker, const rtv::Variant& f, bool
       << ", true>::value)) void rt_trace_jit(TraceParams P) {\n"
       << "  trace_body<false, " << b(f.vol) << ", " << b(f.tex) << ", " << b(f.bvh) << ", "
       << b(f.staged) << ", " << b(f.volb) << ", " << b(f.voli) << ", TravGen"
-      // the plain kernel's text stays as it was: the flag is part of the source (and so of the
-      // module cache's and the code-object cache's keys) only when set
-      << (tiles ? ", true" : "") << ">(P);\n}\n";
+      // the plain kernel's text stays as it was: the launch kind is part of the source (and so of
+      // the module cache's and the code-object cache's keys) only when it is not the plain one
+      << (launch == 1 ? ", kLaunchTiles" : launch == 2 ? ", kLaunchRays" : "") << ">(P);\n}\n";
   return src.str();
 }
 
@@ -938,9 +938,9 @@ void release_kernel(const Kernel& k) {
   evict_idle_locked();
 }
 
-int get_kernel(const std::string& walker, int device, const rtv::Variant& v, bool tiles,
+int get_kernel(const std::string& walker, int device, const rtv::Variant& v, int launch,
                Kernel* out, std::string* log) {
-  const std::string s = kernel_source(walker, v, tiles);
+  const std::string s = kernel_source(walker, v, launch);
   std::lock_guard<std::mutex> lock(g_mu);
   // compile() reads RT_JIT_SRC_DIR's headers and RT_JIT_OPTS's options when set (diagnostics):
   // part of the module's identity, so an A/B in one process gets one module per setting

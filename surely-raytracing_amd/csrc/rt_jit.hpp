@@ -21,10 +21,10 @@ std::string generate(const rtf::FlatScene& F, std::string* why);
 // The generated walker runs in the path kernel (rt_kernel.h trace_body) with the scene's variant
 // (rt_variant.h choose_variant): the template arguments and launch bounds of the ahead-of-time
 // interpreter kernel the scene would otherwise launch. generate() refuses scenes with nested
-// volumes, so a variant's vn never reaches the source. tiles: the tile-list variant (trace_body's
-// TILES; rt_render_tiles_device).
+// volumes, so a variant's vn never reaches the source. launch: trace_body's LK, 0 the plain kernel, 1 the
+// tile-list variant (rt_render_tiles_device), 2 the ray variant (rt_render_rays_device).
 
-// Kernel for (generated walker, variant, tiles) on `device`, compiled on first use and cached for
+// Kernel for (generated walker, variant, launch kind) on `device`, compiled on first use and cached for
 // the process. Returns 0 or a negative rt status with *log filled.
 struct Kernel {
   hipModule_t mod = nullptr;
@@ -34,7 +34,7 @@ struct Kernel {
   int regs = 0, max_threads = 0, static_lds = 0, scratch = 0;
   bool cached = false;  // loaded from the code-object cache (rt_jit.cpp cache_path), not compiled
 };
-int get_kernel(const std::string& walker, int device, const rtv::Variant& v, bool tiles,
+int get_kernel(const std::string& walker, int device, const rtv::Variant& v, int launch,
                Kernel* out, std::string* log);
 // A scene's hold on a kernel from get_kernel ends (rt_scene_destroy). The process-wide cache keeps
 // every kernel some scene holds, plus up to kIdleModules unheld ones for scenes created again
@@ -45,7 +45,7 @@ void release_kernel(const Kernel& k);
 // The hiprtc translation unit (embedded headers + walker + rt_trace_jit wrapper) and its
 // compilation for `arch` (e.g. "gfx950") into a code object; host-only, no device needed.
 // use_cache = false bypasses the code-object cache (a cached entry that failed to load).
-std::string kernel_source(const std::string& walker, const rtv::Variant& v, bool tiles);
+std::string kernel_source(const std::string& walker, const rtv::Variant& v, int launch);
 int compile(const std::string& src, const std::string& arch, std::vector<char>* code,
             std::string* log, bool use_cache = true);
 

@@ -411,7 +411,22 @@ struct TraceParams {
   // LDS byte offset (row pools only when the plan placed them: n_pairs_r = 0 otherwise)
   uint32_t row_lds_off;
   uint32_t o_mats, o_texs, o_lights, o_loffs, o_perl;
-  double center[3], p00[3], du[3], dv[3], ddu[3], ddv[3], bg[3];
+  double center[3], p00[3], du[3], dv[3];
+  // Ray launches (trace_body<..., kLaunchRays>, rt_render_rays_device) form no camera ray, and
+  // their constants take the place of the defocus disk's u vector, so the struct, and with it the
+  // kernarg segment of every plain and tile-list kernel, is what it was: the caller's 80-byte
+  // rt_ray records as five uint4 each. The batch is laid out as an image 8 pixels wide, so tile t
+  // is rays 64 t .. 64 t + 63 and an item's key is its ray index; n_sj = sqrt_spp = S, and sample
+  // (s_j, s_i) of a ray is its path s_j * S + s_i. rays_skip generator steps are discarded before
+  // a path starts; with RT_RAYS_STREAM_TIME in rays_mode the last of them is the path's time.
+  union {
+    double ddu[3];
+    struct {
+      const uint4* rays;
+      uint32_t n_rays, rays_skip, rays_mode, rays_pad;
+    };
+  };
+  double ddv[3], bg[3];
   float bg_w[3];  // (float)bg: the background as the path kernel's f32 weight
   double rs;
   int defocus;
@@ -424,6 +439,10 @@ struct TraceParams {
   const uint32_t* __restrict__ tile_list;
   int sj_step;
 };
+
+// Where a launch's pools take their pixels from (trace_body's LK): the call's tile grid, a list of
+// its tiles (rt_render_tiles_device), or a batch of caller-supplied rays (rt_render_rays_device).
+constexpr int kLaunchPlain = 0, kLaunchTiles = 1, kLaunchRays = 2;
 
 // The kernel's only argument sits at offset 0 of the kernarg segment. Camera constants are read
 // through this pointer at their point of use; the empty asm makes the pointer opaque so the loads
@@ -588,6 +607,8 @@ __device__ __forceinline__ double comp(d3 v) {
 __device__ __forceinline__ double hilo(uint32_t lo, uint32_t hi) {
   return __hiloint2double((int)hi, (int)lo);
 }
+// the exponent field of a double's high word is not all ones
+__device__ __forceinline__ bool finite_hi(uint32_t hi) { return (hi & 0x7ff00000u) != 0x7ff00000u; }
 struct AQuad {  // the first 64 bytes of a world QUAD record
   uint32_t h0;
   double qk, lo0, lo1, hi0, hi1;  // accepted hit-point coordinates per in-plane axis (rt_layout.h)
@@ -2251,9 +2272,13 @@ __device__ __forceinline__ void make_tabs(const TraceParams& P,
 // TILES: the launch's pairs are compact over a host-validated list of tiles and a strided set of
 // stratum rows (TraceParams::tile_list, sj_step); only the pixel coordinates and the stratum row of
 // the RNG key and jitter come from them, every pair, slot and pool index stays the position in the list.
+// RAYS: a lane's item is one caller-supplied ray (TraceParams::rays) and its samples are the ray's
+// paths; the camera-ray block reads the ray instead of forming one, and the claim loop, bounce
+// loop, workspace and reduction are the plain launch's. LK: kLaunchPlain, kLaunchTiles, kLaunchRays.
 template <bool COUNT, bool VOL, bool TEX, bool BVH, bool STAGED, bool VOLB, bool VOLI, class Trav,
-          bool TILES = false>
+          int LK = kLaunchPlain>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
+  constexpr bool TILES = LK == kLaunchTiles, RAYS = LK == kLaunchRays;
   // STAGED: the small-table prefix is in LDS (P.stage_scene) and per-lane table reads are
   // ds_reads through 32-bit LDS pointers; otherwise they read the global tables.
   typedef typename cond<STAGED, lptr, gptr>::type TP;
@@ -2456,10 +2481,17 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         const int ent = q / Q->n_sj;  // the pair's tile: its index, or its position in the list
         int tile = ent;
         if constexpr (TILES) tile = (int)Q->tile_list[ent];
-        tx = tile % Q->tiles_x;
-        ty = tile / Q->tiles_x;
-        tile_w = imin(kWaveTile, Q->W - tx * kWaveTile);
-        nv = tile_w * imin(kWaveTile, Q->n_rows - ty * kWaveTile);
+        if constexpr (RAYS) {  // tx: the tile's first ray; the last tile holds the batch's rest
+          tx = tile * (kWaveTile * kWaveTile);
+          ty = 0;
+          tile_w = kWaveTile;
+          nv = imin(kWaveTile * kWaveTile, (int)Q->n_rays - tx);
+        } else {
+          tx = tile % Q->tiles_x;
+          ty = tile / Q->tiles_x;
+          tile_w = imin(kWaveTile, Q->W - tx * kWaveTile);
+          nv = tile_w * imin(kWaveTile, Q->n_rows - ty * kWaveTile);
+        }
         si0 = blk * kPoolSi;
         pool = tailp ? nv * imin(kPoolSi, Q->sqrt_spp - si0) : nv;
         if constexpr (TILES)
@@ -2496,11 +2528,22 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         }
         const int x = tx * kWaveTile + cx;
         const int kr = ty * kWaveTile + cy;
-        xk = (uint32_t)x | (uint32_t)kr << 16 | (tailp ? 0x80000000u : 0u);
+        if constexpr (RAYS)  // the item's key is its ray index (pv < nv keeps it below n_rays)
+          xk = (uint32_t)(tx + pv) | (tailp ? 0x80000000u : 0u);
+        else
+          xk = (uint32_t)x | (uint32_t)kr << 16 | (tailp ? 0x80000000u : 0u);
         sij = (rowp ? 0x80000000u : 0u) | (uint32_t)s_jp << 16 | (uint32_t)s_i;
         oslot = obase + (tailp ? (uint32_t)s_i * 64u : 0u) + (uint32_t)pv;
         sh_acc[tid] = 0.0, sh_acc[NB + tid] = 0.0, sh_acc[2 * NB + tid] = 0.0;
-        if constexpr (SPLITKEY) {
+        if constexpr (SPLITKEY && RAYS) {
+          // the stream key's pixel and sample terms from the ray's own (pixel, sample): path k of
+          // the ray is sample ray.sample + k (mod 2^32), so the item's next path is still one add
+          const kparams_t Q = kparams();
+          const uint4 r4 = Q->rays[(size_t)(tx + pv) * 5u + 4u];
+          sh_key[tid] = rng_key_pixel(Q->seed_lo, r4.z);
+          sh_key[NB + tid] = rng_key_sample(Q->seed_lo, Q->seed_hi,
+                                            r4.w + (uint32_t)(s_jp * Q->sqrt_spp + s_i));
+        } else if constexpr (SPLITKEY) {
           const kparams_t Q = kparams();
           const int y = Q->row_begin + kr * Q->row_step;
           sh_key[tid] = rng_key_pixel(Q->seed_lo, (uint32_t)(y * Q->W + x));
@@ -2529,7 +2572,50 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       asm volatile("" ::"v"(ps.x), "v"(ps.y), "v"(ps.z), "v"(t2));
     }
 #endif
-    if (fresh) {
+    if constexpr (RAYS) {
+      if (fresh) {
+        // The caller's ray (rt_mi355x.h, rt_render_rays_device) instead of get_ray: 16-byte loads
+        // of its 80 bytes (the fifth, pixel and sample, at the claim where the key is split),
+        // validity from the high words (an infinity or NaN has all exponent bits set), as
+        // rt_query.h decodes it. tmin / tmax are not read: ray_color's interval is [1e-4, inf).
+        const kparams_t Q = kparams();
+        const uint4* R = Q->rays + (size_t)(xk & 0x7fffffffu) * 5u;
+        const uint4 r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3];
+        const bool dir0 = ((r1.z | r2.x | r2.z) == 0u) & (((r1.w | r2.y | r2.w) & 0x7fffffffu) == 0u);
+        const bool valid = finite_hi(r0.y) && finite_hi(r0.w) && finite_hi(r1.y) &&
+                           finite_hi(r1.w) && finite_hi(r2.y) && finite_hi(r2.w) &&
+                           finite_hi(r3.y) && !dir0;  // origin, dir, time
+        if constexpr (SPLITKEY) {  // the ray's paths are consecutive samples of its stream key
+          const uint32_t v1 = sh_key[NB + tid];
+          g = rng_key_mix(sh_key[tid], v1);
+          sh_key[NB + tid] = rng_key_next(v1);
+        } else {
+          const uint4 r4 = R[4];
+          const int s_i = (int)(sij & 0xffffu), s_j = (int)((sij >> 16) & 0x7fffu);
+          g = rng_seed(Q->seed_lo, Q->seed_hi, r4.z, r4.w + (uint32_t)(s_j * Q->sqrt_spp + s_i));
+        }
+        // rays_skip generator steps are discarded (a host ray generator's jitter and time draws);
+        // the last one is the path's time under RT_RAYS_STREAM_TIME
+        uint32_t last = 0u;
+        for (uint32_t k = Q->rays_skip; k != 0u; --k) last = rng_u32(g);
+        // an invalid ray's lane walks a harmless ray with its wave and never hands its own values
+        // to the walker; the reduction writes NaN over whatever it gathers
+        ro = mk(0., 0., 0.), rd = mk(0., 0., 1.);
+        if (valid) {
+          ro = mk(hilo(r0.x, r0.y), hilo(r0.z, r0.w), hilo(r1.x, r1.y));
+          rd = mk(hilo(r1.z, r1.w), hilo(r2.x, r2.y), hilo(r2.z, r2.w));
+        }
+        if constexpr (Trav::kMoving) {
+          tm = (Q->rays_mode & RT_RAYS_STREAM_TIME) ? (double)last * 0x1p-32 : hilo(r3.x, r3.y);
+          if (!valid) tm = 0.0;
+        }
+        beta = mkw(1, 1, 1);
+        depth = Q->max_depth;  // RT_XS_* cleared
+        alive = true;
+        fresh = false;
+        if (Q->max_depth == 0) end_sample(mk(0., 0., 0.));  // uniform, as the camera-ray block
+      }
+    } else if (fresh) {
       const kparams_t Q = kparams();
       const int x = (int)(xk & 0xffffu);
       const int y = Q->row_begin + (int)((xk >> 16) & 0x7fffu) * Q->row_step;

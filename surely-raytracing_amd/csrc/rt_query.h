@@ -25,8 +25,6 @@ __device__ __forceinline__ uint4 pack2(double a, double b) {
   const unsigned long long y = (unsigned long long)__double_as_longlong(b);
   return make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
 }
-// the exponent field of a double's high word is not all ones
-__device__ __forceinline__ bool finite_hi(uint32_t hi) { return (hi & 0x7ff00000u) != 0x7ff00000u; }
 
 // prim_tab: n_prim record word offsets, ascending, then their n_prim prims (rt_scene::prim_dev)
 __device__ __forceinline__ int prim_of(const uint32_t* __restrict__ prim_tab, uint32_t n_prim,

@@ -125,7 +125,7 @@ struct rt_scene {
   // generated (jit_msg says why), -2 = compile failed (jit_msg = log; the interpreter runs)
   std::string jit_walker, jit_msg;
   int jit_state = -1;
-  rtj::Kernel jit_k[2];  // [tile-list variant] of the scene's one variant (rt_variant.h)
+  rtj::Kernel jit_k[3];  // [launch kind: plain, tile list, rays] of the scene's one variant (rt_variant.h)
   // rt_trace launch timing: one event pair per launch, ring of kTraceRing, tagged by render id
   static constexpr int kTraceRing = 4 * RT_TRACE_HISTORY;
   hipEvent_t tev[kTraceRing][2] = {};
@@ -175,6 +175,8 @@ struct SlotHold {
 // (rt_tiles.hip: its 18 instances compile beside rt_device.hip's); nullptr: RT_VARIANTS has no such row.
 typedef void (*kern_t)(rtk::TraceParams);
 RTS_HIDDEN kern_t tile_trace_kernel(const rtv::Variant& v);
+// The ray variant (trace_body's kLaunchRays; rt_rays.hip, 18 more instances in their own object)
+RTS_HIDDEN kern_t ray_trace_kernel(const rtv::Variant& v);
 
 // What every pass that launches on a scene checks of its camera and row range, with the status
 // codes and rt_last_error() texts; *sj0 / *n_sj: the call's stratum rows sj0 + k * sj_step,

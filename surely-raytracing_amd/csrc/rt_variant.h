@@ -2,11 +2,12 @@
 // template arguments the scene determines, the one function that chooses them, and the one list of
 // the instances that exist. Host only, plain C++ (no HIP; build/variant_check compiles it alone).
 //
-// The launch decides COUNT (RT_FLAG_COUNT_OPS) and TILES (rt_render_tiles_device), the kernel's
+// The launch decides COUNT (RT_FLAG_COUNT_OPS) and the launch kind (plain, rt_render_tiles_device's
+// tile list, rt_render_rays_device's rays), the kernel's
 // origin the walker (the interpreter ahead of time, TravGen in a scene-specialised kernel).
 // Everything that needs the choice calls choose_variant: the render's kernel lookup, the
 // scene-specialised kernel's template arguments and the occupancy cache (rt_device.hip), the
-// tile-list kernels (rt_tiles.hip), the AOV pass (rt_aov.hip: bvh, staged, vn) and the probe
+// tile-list and ray kernels (rt_tiles.hip, rt_rays.hip), the AOV pass (rt_aov.hip: bvh, staged, vn) and the probe
 // (probe/rt_probe_scene.hip).
 #pragma once
 #include <stdint.h>
@@ -59,7 +60,7 @@ inline Variant choose_variant(const rtl_scene_header& hdr, uint32_t flags, bool 
 }  // namespace rtv
 
 // The instances that exist: X(vol, tex, bvh, staged, volb, voli, vn), every Variant that
-// choose_variant can return. rt_device.hip and rt_tiles.hip instantiate their kernels from these
+// choose_variant can return. rt_device.hip, rt_tiles.hip and rt_rays.hip instantiate their kernels from these
 // rows and build their lookup (by equality on the Variant) from the same tokens. The op-counting
 // kernels exist for the rows with voli (choose_variant never clears it under RT_FLAG_COUNT_OPS).
 #define RT_VARIANTS(X)                                                               \

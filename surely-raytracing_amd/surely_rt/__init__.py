@@ -154,6 +154,27 @@ class RtQueryParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("flags", C.c_uint32), ("mode", C.c_uint32)]
 
 
+class RtRaysParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("flags", C.c_uint32), ("mode", C.c_uint32),
+                ("sqrt_paths", C.c_int32), ("max_depth", C.c_int32),
+                ("stream_skip", C.c_uint32), ("_pad0", C.c_uint32),
+                ("background", C.c_double * 3)]
+
+
+class RthProjection(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("sqrt_spp", C.c_int32), ("origin", C.c_double * 3),
+                ("forward", C.c_double * 3), ("up", C.c_double * 3), ("fov", C.c_double)]
+
+
+# ray renders (rt_render_rays*)
+RT_RAYS_STREAM_TIME = 0x1  # a path's time is the last skipped draw, not ray.time
+RT_RAYS_MAX_SKIP = 16
+# host ray generator (rt_host.h rth_projection_rays)
+RTH_PROJ_PINHOLE, RTH_PROJ_ORTHO, RTH_PROJ_PANORAMA, RTH_PROJ_FISHEYE = 0, 1, 2, 3
+PROJECTIONS = {"pinhole": RTH_PROJ_PINHOLE, "ortho": RTH_PROJ_ORTHO,
+               "panorama": RTH_PROJ_PANORAMA, "fisheye": RTH_PROJ_FISHEYE}
+
 # ray queries (rt_query_rays*): numpy views of rt_ray / rt_hit, 80 bytes each
 RT_QUERY_OCCLUSION = 0x1  # out is one uint8 per ray: 1 hit, 0 miss, 255 invalid
 RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("time", "<f8"), ("tmin", "<f8"),
@@ -173,6 +194,37 @@ def make_rays(origins, dirs, time=0.0, tmin=1e-4, tmax=float("inf"), pixel=None,
     rays["time"], rays["tmin"], rays["tmax"] = time, tmin, tmax
     rays["pixel"] = np.arange(len(o), dtype=np.uint32) if pixel is None else pixel
     rays["sample"] = sample
+    return rays
+
+
+def make_rays_params(seed: int = 1, sqrt_paths: int = 1, max_depth: int = 50,
+                     background=(0.0, 0.0, 0.0), flags: int = RT_FLAG_OVERWRITE,
+                     stream_skip: int = 0, stream_time: bool = False) -> RtRaysParams:
+    """rt_rays_params. stream_skip=3 with stream_time=True renders rays exactly as the camera ray
+    of the same (pixel, sample) key is rendered (projection_rays makes such rays)."""
+    rp = RtRaysParams()
+    rp.seed, rp.flags, rp.mode = seed, flags, RT_RAYS_STREAM_TIME if stream_time else 0
+    rp.sqrt_paths, rp.max_depth, rp.stream_skip = sqrt_paths, max_depth, stream_skip
+    rp.background = _D3(*[float(x) for x in background])
+    return rp
+
+
+def projection_rays(kind, seed: int = 1, s_i: int = 0, s_j: int = 0, cam: "RtCamera | None" = None,
+                    width: int = 0, height: int = 0, sqrt_spp: int = 1, origin=(0.0, 0.0, 0.0),
+                    forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), fov: float = 0.0) -> np.ndarray:
+    """rth_projection_rays: the RAY_DTYPE rays [height * width] of one stratum (s_i, s_j) of a
+    frame. kind: "pinhole" (cam's own rays without its lens), "ortho" (fov = height of the view
+    volume), "panorama" (equirectangular) or "fisheye" (equidistant, fov = full angle in degrees).
+    Render them with make_rays_params(stream_skip=3, stream_time=True)."""
+    pr = RthProjection()
+    pr.kind = PROJECTIONS[kind] if isinstance(kind, str) else int(kind)
+    pr.width, pr.height, pr.sqrt_spp, pr.fov = width, height, sqrt_spp, fov
+    pr.origin, pr.forward, pr.up = _d3(origin), _d3(forward), _d3(up)
+    if pr.kind == RTH_PROJ_PINHOLE and cam is not None:
+        width, height = cam.image_width, cam.image_height
+    rays = np.zeros(max(0, width) * max(0, height), RAY_DTYPE)
+    _check_host(host_lib().rth_projection_rays(C.byref(pr), C.byref(cam) if cam is not None else None,
+                                               seed, s_i, s_j, rays.ctypes.data))
     return rays
 
 
@@ -243,6 +295,8 @@ def host_lib() -> C.CDLL:
             "rth_auto_expose": (f64, [C.c_void_p, C.c_int64, i32]),
             "rth_write_color": (C.c_int, [C.c_void_p, C.c_int64, f64, C.c_int, f64, C.c_void_p]),
             "rth_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, i32, i32]),
+            "rth_projection_rays": (C.c_int, [C.POINTER(RthProjection), C.POINTER(RtCamera),
+                                              C.c_uint64, i32, i32, C.c_void_p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -370,6 +424,10 @@ def load_device_lib(path: Path) -> C.CDLL:
         "rt_scene_prim_map": (C.c_int, [C.POINTER(RtSceneBlob), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_uint32,
                                         C.POINTER(C.c_uint32)]),
+        "rt_render_rays_device": (C.c_int, [p, C.POINTER(RtRaysParams), C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_render_rays": (C.c_int, [p, C.POINTER(RtRaysParams), C.c_void_p, C.c_uint64,
+                                     C.c_void_p, C.POINTER(RtStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -737,6 +795,32 @@ class DeviceScene:
         st = RtStats() if stats else None
         _check_dev(self._lib.rt_query_rays_device(
             self._h, C.byref(qp), C.c_void_p(rays_ptr), n, C.c_void_p(out_ptr),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
+        return st
+
+    def render_rays(self, rays: np.ndarray, params: RtRaysParams, rgb: np.ndarray | None = None,
+                    stats: bool = False):
+        """Synchronous rt_render_rays: the path-traced radiance sums of a RAY_DTYPE array
+        (make_rays, projection_rays) under `params` (make_rays_params) as float32 [n, 3]. Without
+        RT_FLAG_OVERWRITE the sums are added into `rgb`. An invalid ray's three values are NaN.
+        Returns rgb, or (rgb, stats) with stats=True."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        if rgb is None:
+            rgb = np.zeros((len(rays), 3), np.float32)
+        assert rgb.shape == (len(rays), 3) and rgb.dtype == np.float32 and rgb.flags.c_contiguous
+        st = RtStats()
+        if len(rays):
+            _check_dev(self._lib.rt_render_rays(self._h, C.byref(params), rays.ctypes.data,
+                                                len(rays), rgb.ctypes.data, C.byref(st)))
+        return (rgb, st) if stats else rgb
+
+    def render_rays_device(self, rays_ptr: int, n: int, rgb_ptr: int, params: RtRaysParams,
+                           stream: int = 0, stats: bool = False):
+        """Asynchronous rt_render_rays_device: n rt_ray records at rays_ptr (16-byte aligned, e.g.
+        a torch tensor's data_ptr()) into n * 3 floats at rgb_ptr, on `stream`."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_render_rays_device(
+            self._h, C.byref(params), C.c_void_p(rays_ptr), n, C.c_void_p(rgb_ptr),
             C.c_void_p(stream or None), C.byref(st) if st is not None else None))
         return st
 

@@ -24,6 +24,8 @@ def main(names):
     os.environ["RT_JIT_CACHE_WRITE"] = "1"
     # also each kernel's tile-list variant (rt_render_tiles_device, the adaptive driver)
     os.environ["RT_JIT_CHECK_TILES"] = "1"
+    # and its ray variant (rt_render_rays_device)
+    os.environ["RT_JIT_CHECK_RAYS"] = "1"
     cache = REPO / "build" / "jit_cache"
     cache.mkdir(parents=True, exist_ok=True)
     todo = [(n, kw) for n, kw in SCENES if not names or n in names]
