@@ -303,9 +303,11 @@ int rt_render_multi(const rt_scene_blob* blob, const rt_camera* cam, const rt_re
  * de-interleaves them into accum_rgb_device0 (a devices[0] buffer of opts->n_rows * W * 3
  * floats; overwritten or added to as opts->flags says). Asynchronous on hip_stream (a devices[0]
  * stream, may be NULL); stats != NULL synchronises it. Bit for bit the image of rt_render_device
- * on one device. Consecutive frames of one handle are ordered on devices[0] (a frame waits for the
- * previous frame's gather, whatever stream each was issued on); calls from several host threads
- * are serialised. rt_multi_info: out[0..3] = frames rendered, scene uploads, staging-buffer
+ * on one device, for any number of rows (the de-interleave kernel loops over the rows beyond a
+ * grid's 65535 blocks in y, and every device splits its share as rt_render_device does).
+ * Consecutive frames of one handle are ordered on devices[0] (a frame waits for the previous
+ * frame's gather, whatever stream each was issued on); calls from several host threads are
+ * serialised. rt_multi_info: out[0..3] = frames rendered, scene uploads, staging-buffer
  * allocations, devices. */
 typedef struct rt_multi rt_multi;
 int rt_multi_create(const rt_scene_blob* blob, const int* devices, int n_devices, rt_multi** out);

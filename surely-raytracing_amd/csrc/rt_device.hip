@@ -281,19 +281,22 @@ __global__ __launch_bounds__(256) void rt_reduce(const double* __restrict__ part
 __global__ __launch_bounds__(256) void rt_deinterleave(float* __restrict__ stage,
                                                        float* __restrict__ frame, int row_floats,
                                                        int n_rows, int G, int to_frame) {
-  const int kr = blockIdx.y;  // row of the frame
-  if (kr >= n_rows) return;
-  const int k = kr % G, j = kr / G;
-  // device k's rows start at sum_{k' < k} rows(k'), rows(k') = ceil((n_rows - k') / G)
-  int row0 = 0;
-  for (int q = 0; q < k; ++q) row0 += (n_rows - q + G - 1) / G;
-  float* st = stage + (size_t)(row0 + j) * row_floats;
-  float* fr = frame + (size_t)kr * row_floats;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < row_floats; i += gridDim.x * blockDim.x) {
-    if (to_frame)
-      fr[i] = st[i];
-    else
-      st[i] = fr[i];
+  // kr: row of the frame (a grid's y extent ends at 65535 blocks, so taller frames loop; the
+  // same shape as rt_gather_deinterleave_k)
+  for (int kr = blockIdx.y; kr < n_rows; kr += gridDim.y) {
+    const int k = kr % G, j = kr / G;
+    // device k's rows start at sum_{k' < k} rows(k'), rows(k') = ceil((n_rows - k') / G)
+    int row0 = 0;
+    for (int q = 0; q < k; ++q) row0 += (n_rows - q + G - 1) / G;
+    float* st = stage + (size_t)(row0 + j) * row_floats;
+    float* fr = frame + (size_t)kr * row_floats;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < row_floats;
+         i += gridDim.x * blockDim.x) {
+      if (to_frame)
+        fr[i] = st[i];
+      else
+        st[i] = fr[i];
+    }
   }
 }
 
@@ -1671,8 +1674,9 @@ int rt_multi_render(rt_multi* m, const rt_camera* cam, const rt_render_opts* opt
   if (e != hipSuccess) return fail(e, "staging buffer");
   const bool accumulate = !(opts->flags & RT_FLAG_OVERWRITE);
   const int gx = (int)std::min<size_t>(64, (row_floats + 255) / 256);
+  const int gy = std::min(opts->n_rows, 65535);  // rt_deinterleave loops over the rest
   if (accumulate) {  // the caller's rows to the staging area: each device accumulates its own
-    hipLaunchKernelGGL(rt_deinterleave, dim3((unsigned)gx, (unsigned)opts->n_rows), dim3(256), 0,
+    hipLaunchKernelGGL(rt_deinterleave, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
                        out_stream, m->stage, accum_rgb_device0, (int)row_floats, opts->n_rows, G, 0);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(e, "scatter");
@@ -1728,7 +1732,7 @@ int rt_multi_render(rt_multi* m, const rt_camera* cam, const rt_render_opts* opt
     for (int k = 0; k < G && e == hipSuccess; ++k)
       if (used[k]) e = hipStreamWaitEvent(out_stream, m->dev[k].done, 0);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(rt_deinterleave, dim3((unsigned)gx, (unsigned)opts->n_rows), dim3(256), 0,
+      hipLaunchKernelGGL(rt_deinterleave, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
                          out_stream, m->stage, accum_rgb_device0, (int)row_floats, opts->n_rows, G, 1);
       e = hipGetLastError();
     }

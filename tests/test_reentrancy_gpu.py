@@ -129,3 +129,110 @@ def test_per_thread_default_stream_from_two_threads(gpu_available):
     assert not errors, errors
     for s in seeds:
         assert np.array_equal(got[s], serial[s])
+
+
+# ------------------------------------------------------------------ more streams than slots
+# A scene keeps at most rt_scene::kMaxSlots = 8 render slots (acquire_slot, rt_device.hip). Twelve
+# renders of one scene on twelve streams, issued back to back from one thread without stats or
+# synchronisation: from the ninth on, a call finds no new slot to make and takes a slot an earlier
+# render used (after that render's event, which its stream also waits for), with that slot's
+# pool-queue word, counters and workspace. Every buffer must still hold its serial image.
+N_STREAMS = 12
+
+
+def _issue_all(jobs, streams):
+    """Every job's call once, back to back, then all streams synchronised."""
+    for job, st in zip(jobs, streams):
+        job(st.handle)
+    for st in streams:
+        st.sync()
+
+
+def test_twelve_streams_share_eight_slots(gpu_available):
+    from hip_buf import DevBuf, Stream
+
+    blob, cam = rt.preset_blob("cornell_box", width=40, spp=16, aspect=40.0 / 24.0)
+    assert (cam.image_width, cam.image_height, cam.samples_per_pixel) == (40, 24, 16)
+    ds = rt.DeviceScene(blob)
+    seeds = list(range(41, 41 + N_STREAMS))
+    serial = [ds.render(cam, rt.make_opts(cam, seed=s))[0] for s in seeds]
+    assert len({a.tobytes() for a in serial}) == N_STREAMS
+    streams = [Stream() for _ in range(N_STREAMS)]
+    bufs = [DevBuf(serial[0].shape) for _ in range(N_STREAMS)]
+    jobs = [lambda h, s=s, b=b: ds.render_device(cam, rt.make_opts(cam, seed=s), b.ptr, h)
+            for s, b in zip(seeds, bufs)]
+    try:
+        for rnd in range(2):  # the second round meets slots with a recorded event
+            for b in bufs:
+                b.upload(np.full(b.shape, -7.0, np.float32))
+            _issue_all(jobs, streams)
+            for k, (b, ref) in enumerate(zip(bufs, serial)):
+                assert np.array_equal(b.download(), ref), f"round {rnd}, stream {k}"
+    finally:
+        for b in bufs:
+            b.free()
+        for st in streams:
+            st.destroy()
+        ds.close()
+
+
+def test_mixed_shapes_pass_through_shared_slots(gpu_available):
+    """64x64 and 8x8 frames alternate over the twelve streams, so a reused slot's workspace is
+    in turn larger and smaller than the render needs; one of the renders is a moments render
+    (the slot's second workspace) and one a tile-list render (the slot's tile list)."""
+    from hip_buf import DevBuf, Stream
+
+    blob, big = rt.preset_blob("cornell_box", width=64, spp=16)
+    _, small = rt.preset_blob("cornell_box", width=8, spp=16)
+    assert (big.image_height, small.image_height) == (64, 8)
+    ds = rt.DeviceScene(blob)
+    tiles = np.array([0, 3, 9, 36, 63], np.uint32)  # of the 8 x 8 tile grid of the 64x64 frame
+    S = big.sqrt_spp
+    MOMENTS, TILES = 4, 6  # two of the 64x64 jobs
+    fill = np.float32(0.5)
+
+    def make(k, bufs):
+        cam = big if k % 2 == 0 else small
+        if k == MOMENTS:
+            return lambda h: ds.render_moments_device(cam, rt.make_opts(cam, seed=60 + k),
+                                                      bufs[0].ptr, bufs[1].ptr, h)
+        if k == TILES:
+            opts = rt.make_opts(cam, seed=60 + k, sj_begin=0, sj_count=S)
+            return lambda h: ds.render_tiles_device(cam, opts, tiles, 1, bufs[0].ptr,
+                                                    bufs[1].ptr, h)
+        return lambda h: ds.render_device(cam, rt.make_opts(cam, seed=60 + k), bufs[0].ptr, h)
+
+    def buffers(k):
+        cam = big if k % 2 == 0 else small
+        shape = (cam.image_height, cam.image_width, 3)
+        n = 2 if k in (MOMENTS, TILES) else 1
+        return [DevBuf(shape, init=np.full(shape, fill, np.float32)) for _ in range(n)]
+
+    streams = [Stream() for _ in range(N_STREAMS)]
+    bufs = [buffers(k) for k in range(N_STREAMS)]
+    ref_bufs = [buffers(k) for k in range(N_STREAMS)]
+    try:
+        serial = []
+        for k in range(N_STREAMS):  # one at a time, each synchronised before the next
+            make(k, ref_bufs[k])(0)
+            serial.append([b.download() for b in ref_bufs[k]])
+        # tile row 2 (rows 16-23) holds no listed tile; tile 0 is rows and columns 0-7
+        assert (serial[TILES][0][16:24] == fill).all()
+        assert not (serial[TILES][0][:8, :8] == fill).any()
+        assert serial[MOMENTS][1].any() and not np.array_equal(serial[0][0], serial[2][0])
+        jobs = [make(k, bufs[k]) for k in range(N_STREAMS)]
+        for rnd in range(2):
+            for bb in bufs:
+                for b in bb:
+                    b.upload(np.full(b.shape, fill, np.float32))
+            _issue_all(jobs, streams)
+            for k in range(N_STREAMS):
+                for b, ref in zip(bufs[k], serial[k]):
+                    assert np.array_equal(b.download(), ref), f"round {rnd}, stream {k}"
+    finally:
+        for bb in bufs + ref_bufs:
+            for b in bb:
+                b.free()
+        for st in streams:
+            st.destroy()
+        ds.close()
