@@ -140,6 +140,28 @@ typedef struct rth_projection {   /* 96 bytes, no padding */
 int rth_projection_rays(const rth_projection* proj, const rt_camera* cam /* pinhole only */,
                         uint64_t seed, int32_t s_i, int32_t s_j, rt_ray* out);
 
+/* Host generator of ambient-occlusion ray batches for any-hit queries (rt_mi355x.h, RT_QUERY_ANY_HIT):
+ * from a batch of primary rays and their records (rt_query_rays, record mode), the k-th of K
+ * cosine-distributed directions about each hit's normal. For ray i with hits[i].hit == 1 the
+ * generator rng_seed(seed, primary[i].pixel, dir_index) (csrc/rt_rng.h) supplies r1 and r2, the local
+ * direction is random_cosine_direction's (vec3.rs:240-250), the frame Onb::build_from_w(hits[i].
+ * normal) (onb.rs:32-47) and dir = local(x, y, z) (unit length to rounding, dir . normal >= 0);
+ * origin = hits[i].p, time = primary[i].time, tmin = p->tmin, tmax = p->radius, pixel = primary[i].
+ * pixel, sample = dir_index. For any other hits[i].hit, dir is all zero and origin 0 (the other
+ * fields as above): an invalid ray, which the query answers with 255. A pixel's ambient occlusion
+ * is then unoccluded / K over K batches. out may be primary.
+ * Returns 0, or -1 (rth_last_error): null arguments, a tmin that is not finite or < 0, a radius
+ * that is NaN or <= tmin, _pad0 != 0. */
+typedef struct rth_ao_params {   /* 32 bytes, no padding */
+  uint64_t seed;
+  double radius;       /* becomes tmax; > tmin, may be +inf; NaN invalid */
+  double tmin;         /* finite, >= 0; 1e-4 is the reference's */
+  uint32_t dir_index;  /* k: which of the K directions this batch is */
+  uint32_t _pad0;      /* must be 0 */
+} rth_ao_params;
+int rth_ao_rays(const rt_ray* primary, const rt_hit* hits, uint64_t n, const rth_ao_params* p,
+                rt_ray* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -833,15 +833,30 @@ int  rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const r
  * with its wave); its record is hit = -1 and every other field 0, in occlusion mode the byte 255.
  * The other rays' records are unaffected and the call returns RT_OK.
  *
+ * Any-hit mode (mode == RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT): the users of occlusion mode (shadow
+ * rays, ambient occlusion, visibility between two points, lidar returns) need no closest hit, only
+ * whether anything lies in [tmin, tmax]. The any-hit walk leaves at the first primitive that accepts
+ * and writes, for every ray, the byte RT_QUERY_OCCLUSION alone writes for the same ray and params
+ * (1, 0, or 255 for an invalid ray), with and without RT_FLAG_REFERENCE_BVH and on scenes with
+ * ConstantMedium records. Why the bytes are equal: a primitive's accept test is monotone in the
+ * upper end of the interval (a quad's t <= closest, a sphere's choice of root: whatever accepts
+ * under a smaller upper end accepts under a larger one), so "some primitive accepts in
+ * [tmin, tmax]" is the closest-hit walk's final hit flag. Up to the first accept both walks see the
+ * same interval and the same generator state, so a ConstantMedium draws the same numbers, and after
+ * the first accept the closest-hit flag never goes back to false. A ray with tmax < tmin can be
+ * accepted by nothing and leaves at once (byte 0). Argument checks, slots, stream order and rt_stats
+ * are those of occlusion mode. The bit is valid only together with RT_QUERY_OCCLUSION: any-hit has
+ * no record to fill.
+ *
  * Checked before the scene is read and before any HIP call, RT_ERR_INVALID_ARG each: a null scene,
  * params, rays or out; n_rays >= 2^31; flag bits other than RT_FLAG_REFERENCE_BVH; mode bits other
- * than RT_QUERY_OCCLUSION; rays not 16-byte aligned; out not 16-byte aligned in record mode.
+ * than RT_QUERY_OCCLUSION and RT_QUERY_ANY_HIT, or RT_QUERY_ANY_HIT without RT_QUERY_OCCLUSION; rays
+ * not 16-byte aligned; out not 16-byte aligned in record mode.
  * n_rays == 0 returns RT_OK and touches nothing. Slots, stream ordering, re-entrancy and lifetime
  * are those of rt_render_aov_device. rt_stats: ms_kernel, ms_total; samples = n_rays; launches = 1;
  * out_bytes = bytes written (80 or 1 per ray); ops all zero.
  *
- * Not covered: an any-hit early exit (occlusion mode runs the closest-hit walk and writes less);
- * u, v, albedo or emission at the hit; the scene-specialised hiprtc walker, whose interval is
+ * Not covered: u, v, albedo or emission at the hit; the scene-specialised hiprtc walker, whose interval is
  * fixed; rt_multi_*. */
 typedef struct rt_ray {        /* 80 bytes, no padding */
   double origin[3];
@@ -863,11 +878,14 @@ typedef struct rt_hit {        /* 80 bytes, no padding */
 } rt_hit;
 
 #define RT_QUERY_OCCLUSION 0x1u   /* out is one uint8 per ray: 1 hit, 0 miss, 255 invalid */
+#define RT_QUERY_ANY_HIT 0x2u     /* with RT_QUERY_OCCLUSION only: the same bytes from a walk that
+                                     leaves at the first accepted primitive */
 
 typedef struct rt_query_params {  /* 16 bytes */
   uint64_t seed;
   uint32_t flags;              /* RT_FLAG_REFERENCE_BVH only; any other RT_FLAG_* bit is RT_ERR_INVALID_ARG */
-  uint32_t mode;               /* 0 or RT_QUERY_OCCLUSION; unknown bits RT_ERR_INVALID_ARG */
+  uint32_t mode;               /* 0, RT_QUERY_OCCLUSION or RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT;
+                                  anything else RT_ERR_INVALID_ARG */
 } rt_query_params;
 
 /* asynchronous on hip_stream (may be NULL): device buffers; stats != NULL synchronises */

@@ -81,6 +81,7 @@ pub const RT_TEMPORAL_VARIANCE_OF_MEAN: u32 = 0x2;
 
 // ray queries
 pub const RT_QUERY_OCCLUSION: u32 = 0x1;
+pub const RT_QUERY_ANY_HIT: u32 = 0x2; // with RT_QUERY_OCCLUSION only
 
 // ray renders
 pub const RT_RAYS_STREAM_TIME: u32 = 0x1;
@@ -252,7 +253,7 @@ pub struct rt_hit {
 pub struct rt_query_params {
     pub seed: u64,
     pub flags: u32, // RT_FLAG_REFERENCE_BVH only
-    pub mode: u32,  // 0 or RT_QUERY_OCCLUSION
+    pub mode: u32,  // 0, RT_QUERY_OCCLUSION or RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT
 }
 
 /// Parameters of rt_render_rays*; 56 bytes, no padding.

@@ -358,6 +358,51 @@ int rth_projection_rays(const rth_projection* pr, const rt_camera* cam, uint64_t
   return 0;
 }
 
+// ---- rth_ao_rays: ambient-occlusion ray batches for any-hit queries (rt_mi355x.h)
+int rth_ao_rays(const rt_ray* primary, const rt_hit* hits, uint64_t n, const rth_ao_params* p,
+                rt_ray* out) {
+  if (!primary || !hits || !p || !out) return fail("ao_rays: null argument");
+  if (p->_pad0 != 0u) return fail("ao_rays: _pad0 must be 0");
+  if (!(std::isfinite(p->tmin) && p->tmin >= 0.0)) return fail("ao_rays: tmin must be finite and >= 0");
+  if (!(p->radius > p->tmin)) return fail("ao_rays: radius must be > tmin (NaN is invalid)");
+  for (uint64_t i = 0; i < n; ++i) {
+    rt_ray& q = out[i];
+    const rt_hit& h = hits[i];
+    const uint32_t pixel = primary[i].pixel;
+    const double time = primary[i].time;  // read before q is written: out may be primary
+    q.time = time;
+    q.tmin = p->tmin;
+    q.tmax = p->radius;
+    q.pixel = pixel;
+    q.sample = p->dir_index;
+    if (h.hit != 1) {  // no surface: an invalid ray, which the query answers with 255
+      for (int k = 0; k < 3; ++k) q.origin[k] = q.dir[k] = 0.0;
+      continue;
+    }
+    HostRng g = host_rng_seed(p->seed, pixel, p->dir_index);
+    const double r1 = host_rnd(g), r2 = host_rnd(g);
+    // random_cosine_direction (vec3.rs:240-250)
+    const double phi = 2. * M_PI * r1;
+    const double x = std::cos(phi) * std::sqrt(r2), y = std::sin(phi) * std::sqrt(r2);
+    const double z = std::sqrt(1. - r2);
+    // Onb::build_from_w (onb.rs:32-47)
+    double w[3], a[3] = {1., 0., 0.}, wa[3], v[3], u[3];
+    const double wl = std::sqrt(h.normal[0] * h.normal[0] + h.normal[1] * h.normal[1] +
+                                h.normal[2] * h.normal[2]);
+    for (int k = 0; k < 3; ++k) w[k] = h.normal[k] / wl;
+    if (std::fabs(w[0]) > 0.9) a[0] = 0., a[1] = 1.;
+    cross3(w, a, wa);
+    const double vl = std::sqrt(wa[0] * wa[0] + wa[1] * wa[1] + wa[2] * wa[2]);
+    for (int k = 0; k < 3; ++k) v[k] = wa[k] / vl;
+    cross3(w, v, u);
+    for (int k = 0; k < 3; ++k) {
+      q.origin[k] = h.p[k];
+      q.dir[k] = x * u[k] + y * v[k] + z * w[k];  // Onb::local (onb.rs:24-26)
+    }
+  }
+  return 0;
+}
+
 int rth_preset(rth_scene* s, const char* name, const char* variant, int32_t width, int32_t spp,
                int32_t depth, double aspect, int32_t* world_out, int32_t* lights_out,
                rt_camera* cam_out) {

@@ -22,6 +22,10 @@
 //      by rt_render_rays, S * S passes of one path per ray accumulated without RT_FLAG_OVERWRITE;
 //      the output options apply to the frame as to any other (the denoisers, --adaptive, --frames
 //      and --pick need the pinhole camera's AOVs or tiles and do not combine)
+//   -> with --ao K [--ao-radius R]: no path tracing; the pixel-centre rays (as --pick forms them)
+//      go to one record query, then K passes of rth_ao_rays and an any-hit query (RT_QUERY_ANY_HIT)
+//      over [1e-4, R] (default: no limit); a pixel is unoccluded / K in all three channels through
+//      write_color, a pixel that sees no surface 0; does not combine with the render modes
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
@@ -29,6 +33,7 @@
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
 //                      [--device-output] [--frames N] [--orbit DEG] [--temporal] [--out file.ppm]
 //                      [--pick X Y] [--projection ortho|panorama|fisheye] [--fov F]
+//                      [--ao K] [--ao-radius R]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -212,6 +217,72 @@ static int pick_pixel(const rt_scene_blob& blob, const rt_camera& cam, int x, in
   return 0;
 }
 
+// --ao K: ambient occlusion of the first hits. Record query, K x (rth_ao_rays, any-hit query).
+static int render_ao(const rt_scene_blob& blob, const rt_camera& cam, int K, double radius,
+                     uint64_t seed, int device, const std::string& out) {
+  const int W = cam.image_width, H = cam.image_height;
+  const size_t n = (size_t)W * H;
+  // std::vector's allocation is 16-byte aligned for these 80-byte records (operator new)
+  std::vector<rt_ray> primary(n), ao(n);
+  std::vector<rt_hit> hits(n);
+  std::vector<uint8_t> occ(n);
+  std::vector<float> sums(3 * n, 0.0f);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      rt_ray& r = primary[(size_t)y * W + x];
+      std::memset(&r, 0, sizeof(r));
+      for (int k = 0; k < 3; ++k) {
+        r.origin[k] = cam.center[k];
+        r.dir[k] = cam.pixel00_loc[k] + x * cam.pixel_delta_u[k] + y * cam.pixel_delta_v[k] -
+                   cam.center[k];
+      }
+      r.tmin = 1e-4;
+      r.tmax = HUGE_VAL;
+      r.pixel = (uint32_t)(y * W + x);
+    }
+  rt_query_params qp;
+  std::memset(&qp, 0, sizeof(qp));
+  qp.seed = seed;
+  rth_ao_params ap;
+  std::memset(&ap, 0, sizeof(ap));
+  ap.seed = seed;
+  ap.radius = radius;
+  ap.tmin = 1e-4;
+  rt_scene* sc = nullptr;
+  double ms = 0.0;
+  int rc = rt_scene_create(&blob, device, &sc);
+  if (rc == RT_OK) rc = rt_query_rays(sc, &qp, primary.data(), n, hits.data(), nullptr);
+  qp.mode = RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT;
+  for (int k = 0; k < K && rc == RT_OK; ++k) {
+    ap.dir_index = (uint32_t)k;
+    if (rth_ao_rays(primary.data(), hits.data(), n, &ap, ao.data()) != 0) {
+      std::fprintf(stderr, "rth_ao_rays: %s\n", rth_last_error());
+      rt_scene_destroy(sc);
+      return 1;
+    }
+    rt_stats st;
+    rc = rt_query_rays(sc, &qp, ao.data(), n, occ.data(), &st);
+    if (rc != RT_OK) break;
+    ms += st.ms_kernel;
+    for (size_t i = 0; i < n; ++i)
+      if (occ[i] == 0) sums[3 * i] += 1.0f, sums[3 * i + 1] += 1.0f, sums[3 * i + 2] += 1.0f;
+  }
+  rt_scene_destroy(sc);
+  if (rc != RT_OK) {
+    std::fprintf(stderr, "rt_query_rays: %d %s\n", rc, rt_last_error());
+    return 1;
+  }
+  std::vector<uint8_t> rgb(3 * n);
+  rth_write_color(sums.data(), (int64_t)n, (double)K, 0, 1.0, rgb.data());
+  if (rth_write_ppm(out.c_str(), rgb.data(), W, H) != 0) {
+    std::fprintf(stderr, "%s\n", rth_last_error());
+    return 1;
+  }
+  std::fprintf(stderr, "ambient occlusion %dx%d, %d directions, radius %g: %.3f ms in any-hit kernels -> %s\n",
+               W, H, K, radius, ms, out.c_str());
+  return 0;
+}
+
 // --projection: the preset's eye and view frame, another projection. fov <= 0: the height of the
 // pinhole's viewport for ortho, 180 degrees for fisheye. Pixels whose ray is invalid (a fisheye
 // pixel outside the sphere) come back NaN and are written black.
@@ -285,6 +356,8 @@ int main(int argc, char** argv) {
   int frames = 0;  // 0 = one frame, written to --out itself
   double orbit = 0.0;  // degrees per frame
   bool temporal = false;
+  int ao_k = 0;  // > 0: ambient occlusion with ao_k directions per pixel instead of a render
+  double ao_radius = HUGE_VAL;
   bool pick = false;  // one ray query through pixel (pick_x, pick_y) instead of a render
   int pick_x = 0, pick_y = 0;
   int projection = RTH_PROJ_PINHOLE;  // another one: the frame through rt_render_rays
@@ -350,6 +423,13 @@ int main(int argc, char** argv) {
         return 2;
       }
     } else if (a == "--fov") fov = std::atof(next());
+    else if (a == "--ao") {
+      ao_k = std::atoi(next());
+      if (ao_k < 1) {
+        std::fprintf(stderr, "--ao K: K >= 1 directions per pixel\n");
+        return 2;
+      }
+    } else if (a == "--ao-radius") ao_radius = std::atof(next());
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -374,6 +454,17 @@ int main(int argc, char** argv) {
                  "or --pick: they take the pinhole camera's AOVs, tiles or pixels\n");
     return 2;
   }
+  if (ao_k && (denoise_levels || adaptive || frames || pick || projection != RTH_PROJ_PINHOLE ||
+               device_output || autoexp)) {
+    std::fprintf(stderr,
+                 "--ao does not combine with --denoise, --denoise-var, --adaptive, --frames, --pick, "
+                 "--projection, --device-output or --auto-exposure: it renders no radiance\n");
+    return 2;
+  }
+  if (ao_k && !(ao_radius > 1e-4)) {
+    std::fprintf(stderr, "--ao-radius R: R > 1e-4\n");
+    return 2;
+  }
   rth_scene* s = rth_scene_new(build_seed);
   int32_t world = -1, lights = -1;
   rt_camera cam;
@@ -389,6 +480,11 @@ int main(int argc, char** argv) {
   }
   if (pick) {
     const int status = pick_pixel(blob, cam, pick_x, pick_y, seed, device);
+    rth_scene_free(s);
+    return status;
+  }
+  if (ao_k) {
+    const int status = render_ao(blob, cam, ao_k, ao_radius, seed, device, out);
     rth_scene_free(s);
     return status;
   }

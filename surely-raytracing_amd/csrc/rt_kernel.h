@@ -994,8 +994,16 @@ __device__ __forceinline__ bool prof_first_lane() {
 // kparams(). Set for every walk of the nested-volume kernels (TravInterpN<VN > 0>), the only ones
 // so large that the inliner leaves bvh_subtree and a boundary walk as called functions, where
 // kparams() is null. PK = false instantiates the code it always did.
+// ANY (MAIN walks of the any-hit ray query only, rt_query.h): the walk answers whether anything
+// accepts in [tmin, tmax] and leaves at the first accept; t_out, hit_node and hit_frame are then
+// those of that accept, not of the closest hit. An accept test is monotone in the interval's upper
+// end (a quad's t <= closest, a sphere's root choice), so the returned flag is the closest-hit
+// walk's. The UNI walker's node index is wave-uniform, so its exit is too: it keeps a per-lane
+// `done` (set at entry for a lane whose interval is empty, tmax < tmin: nothing can accept there)
+// and leaves once no lane is left. Boundary walks (MAIN = false) stay closest-hit walks: a medium
+// needs both boundary parameters. ANY = false instantiates the code it always did.
 template <bool MAIN, bool COUNT, bool VOL, bool UNI, bool BVH, bool VOLB = VOL, bool VOLI = true,
-          int VN = 0, bool PK = false>
+          int VN = 0, bool PK = false, bool ANY = false>
 __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 wo, d3 wd,
                          double tm, d3 o, d3 d, int frame, double tmin, double tmax,
                          double& t_out, uint32_t& hit_node, int& hit_frame, Rng& g,
@@ -1070,22 +1078,38 @@ __device__ __forceinline__ bool volume_hit(const TraceParams& P, uint32_t node, 
 
 // A BVH subtree [node, stop) walked per lane: its ordered BVH when it has one (obvh != 0),
 // otherwise (and always in the op-counting build) the reference tree in the reference order.
-template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK = false>
+template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK = false, bool ANY = false>
 __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, uint32_t obvh,
                             d3 wo, d3 wd, double tm, d3 o, d3 d, int frame, double tmin,
                             double tmax, double& t_out, uint32_t& hit_node, int& hit_frame,
                             Rng& g, Ctr<COUNT>& C);
 
 template <bool MAIN, bool COUNT, bool VOL, bool UNI, bool BVH, bool VOLB, bool VOLI, int VN,
-          bool PK>
+          bool PK, bool ANY>
 __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 wo, d3 wd,
                          double tm, d3 o, d3 d, int frame, double tmin, double tmax,
                          double& t_out, uint32_t& hit_node, int& hit_frame, Rng& g,
                          Ctr<COUNT>& C) {
   typedef typename cond<UNI, kptr, gptr>::type Ptr;
   const Ptr N = (Ptr)P.nodes;
+  static_assert(!ANY || MAIN, "ANY: MAIN walks only");
   double closest = tmax;
   bool hit = false;
+  // ANY, UNI: the lane has its answer (or an empty interval) and only keeps its wave company
+  [[maybe_unused]] bool done = false;
+  if constexpr (ANY && UNI) done = tmax < tmin;
+  // after a record that can accept: whether the walk ends here, per lane at its first accept, or
+  // wave-uniformly once every lane is done
+  auto any_exit = [&]() -> bool {
+    if constexpr (ANY && UNI) {
+      done = done | hit;
+      return __ballot(!done) == 0ull;
+    } else if constexpr (ANY) {
+      return hit;
+    } else {
+      return false;
+    }
+  };
   // 1/d of the lane's ray in the current frame (Aabb::hit object.rs:347 divides per test; the
   // quotient is the same value every time, so the LANE walker forms it once per frame, by
   // rcp_w: within an ulp, and 1/+-0 = +-inf as the slab test needs)
@@ -1163,7 +1187,9 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
       double t = closest;
       const d3 r = mk(rcp_nr1(d.x), rcp_nr1(d.y), rcp_nr1(d.z));
       bool hq;
-      if (UNI) {
+      if constexpr (ANY && UNI) {  // a done lane takes no further leaf test
+        hq = !done && world_quad_test<COUNT>(X, o, d, r, tmin, closest, t, C);
+      } else if (UNI) {
         hq = world_quad_test<COUNT>(X, o, d, r, tmin, closest, t, C);
       } else {
         const AQuad q = {h.x, hilo(q1.x, q1.y), hilo(q1.z, q1.w), hilo(q2.x, q2.y),
@@ -1177,6 +1203,7 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
         hit_frame = hq ? frame : hit_frame;
       }
       node = h.w;
+      if (any_exit()) break;
     } else if (type == RTL_QUADS) {
       // batch of sibling quads: the same sequential closest-hit updates as the list
       const uint32_t cnt = h.x >> 8;
@@ -1189,7 +1216,9 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
       for (uint32_t k = 0; k < cnt; ++k, Q += RTL_QUAD_WORDS) {
         double t = closest;
         bool hq;
-        if (UNI) {  // scalar loads at the point of use (prefetching them raised SGPR pressure)
+        if constexpr (ANY && UNI) {
+          hq = !done && world_quad_test<COUNT>(Q, o, d, r, tmin, closest, t, C);
+        } else if (UNI) {  // scalar loads at the point of use (prefetching them raised SGPR pressure)
           hq = world_quad_test<COUNT>(Q, o, d, r, tmin, closest, t, C);
         } else {
           const AQuad q = {a0.x, hilo(a1.x, a1.y), hilo(a1.z, a1.w), hilo(a2.x, a2.y),
@@ -1211,9 +1240,17 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
 #ifdef RT_PROF
       if (!UNI) PFW(3, 1);
 #endif
+      // ANY: the batch is finished, not left at its first accept (its quads' loads are in flight
+      // and the winner is a select per quad)
+      if (any_exit()) break;
     } else if (type == RTL_SPHERE) {
       double t = closest;
-      const bool hs = sphere_test<COUNT>(X, o, d, tm, tmin, closest, t, C);
+      bool hs;
+      if constexpr (ANY && UNI) {
+        hs = !done && sphere_test<COUNT>(X, o, d, tm, tmin, closest, t, C);
+      } else {
+        hs = sphere_test<COUNT>(X, o, d, tm, tmin, closest, t, C);
+      }
       closest = t;
       hit = hit | hs;
       if (MAIN) {
@@ -1221,9 +1258,12 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
         hit_frame = hs ? frame : hit_frame;
       }
       node = h.w;
+      if (any_exit()) break;
     } else if (type == RTL_BVH) {
       if (UNI) {
-        if (BVH) {  // the subtree [node, skip) per lane, continuing this walk's closest hit
+        // the subtree [node, skip) per lane, continuing this walk's closest hit (ANY: a done lane
+        // does not enter it; its ballot already runs under a partial exec mask)
+        if (BVH && !(ANY && done)) {
           double t;
           uint32_t hn;
           int hf;
@@ -1231,9 +1271,8 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
           const unsigned long long pt0 = __builtin_readcyclecounter();
           prof_steps[threadIdx.x] = 0u;
 #endif
-          const bool sub = bvh_subtree<MAIN, COUNT, VOLB, BVH, PK>(P, node, h.y, h.w, wo, wd, tm,
-                                                                 o, d, frame, tmin, closest, t,
-                                                                 hn, hf, g, C);
+          const bool sub = bvh_subtree<MAIN, COUNT, VOLB, BVH, PK, ANY>(
+              P, node, h.y, h.w, wo, wd, tm, o, d, frame, tmin, closest, t, hn, hf, g, C);
 #ifdef RT_PROF
           {
             const unsigned long long dt = __builtin_readcyclecounter() - pt0;
@@ -1261,6 +1300,7 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
           }
         }
         node = h.y;
+        if (any_exit()) break;
       }  // LANE: BVH nodes never get here (the while-while step above consumes them)
     } else if (type == RTL_TRANSLATE || type == RTL_ROTATE_Y) {
       C.inc(type == RTL_TRANSLATE ? RT_OP_TRANSLATE : RT_OP_ROTATE_Y);
@@ -1275,7 +1315,10 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
       node = h.w;
     } else if ((MAIN || VN > 0) && VOL && type == RTL_VOLUME) {
       double tv;
-      if (volume_hit<COUNT, UNI, BVH, VOLI, VolTwoInterp, (MAIN ? VN : (VN > 0 ? VN - 1 : 0)), PK>(
+      // ANY: a medium's accepted free-flight hit ends the lane; up to there its draws are the
+      // closest-hit walk's (the same interval, the same generator state)
+      if (!(ANY && UNI && done) &&
+          volume_hit<COUNT, UNI, BVH, VOLI, VolTwoInterp, (MAIN ? VN : (VN > 0 ? VN - 1 : 0)), PK>(
               P, node, h, wo, wd, tm, o, d, frame, tmin, closest, tv, g, C)) {
         closest = tv;
         hit = true;
@@ -1285,6 +1328,7 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
         }
       }
       node = h.y;
+      if (any_exit()) break;
     } else if (type == RTL_DUP) {
       node = COUNT ? h.w : h.y;
     } else if (type == RTL_END) {
@@ -1312,6 +1356,14 @@ __device__ bool traverse(const TraceParams& P, uint32_t node, uint32_t stop, d3 
 // decided by rounding (obvh_far). Boxes are padded bounds and
 // the slab test keeps every box whose entry is <= closest * (1 + kTieRel), so no candidate the
 // flag logic must see is culled.
+// ANY (obvh_walk, cbvh_walk_t; MAIN walks of the any-hit ray query): the lane leaves after the
+// first leaf with a winning candidate (t < tmax; a candidate beyond tmax is not a win), and the
+// flags are evaluated for that winner as they are for the final one: the running closest started
+// at tmax, so the near-tie flag is "the winner lies within the kTieRel window of tmax" (a quad
+// accepts t == tmax, a sphere does not), then the winner within kTieRel of tmin, then obvh_far.
+// An unflagged winner is an accept of the reference-order walk over [tmin, tmax] as well, so the
+// answer is "hit"; a flagged lane, and a lane without a winner whose candidate tied with tmax, is
+// decided by the reference-order any-hit walk (bvh_subtree).
 constexpr double kTieRel = 0x1p-30;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // The exact test of one ordered-BVH leaf record (QUAD, QUADS batch, SPHERE) with the reference
@@ -1462,7 +1514,7 @@ __device__ __forceinline__ bool obvh_far(const gptr N, uint32_t rec, d3 o, d3 d,
   return (h0 & 0xffu) == RTL_SPHERE ? far_s : far_q;
 }
 
-template <bool MAIN>
+template <bool MAIN, bool ANY = false>
 __device__ bool obvh_walk(const TraceParams& P, uint32_t ob, d3 o, d3 d, double tm, int frame,
                           double tmin, double tmax, double& t_out, uint32_t& hit_node,
                           int& hit_frame, bool& flag) {
@@ -1537,6 +1589,9 @@ __device__ bool obvh_walk(const TraceParams& P, uint32_t ob, d3 o, d3 d, double 
     obvh_leaf(N, rec, o, d, r, tm, tmin, cand);
     if (closest != closest_before) close_f = (float)(closest + closest * (2.0 * kTieRel));
     ++e;
+    if constexpr (ANY) {
+      if (hit) break;
+    }
 #ifdef RT_PROF
     ++pf_leaf;
 #endif
@@ -1591,7 +1646,7 @@ __device__ bool obvh_walk(const TraceParams& P, uint32_t ob, d3 o, d3 d, double 
 // box passes when tn <= tf * kBoxPos, one product for box()'s two widenings. It keeps every box
 // the widened test keeps: that test passing means tn (1 - 2^-20)(1 - u) <= tf (1 + 2^-20)(1 + u)
 // (u = 2^-24, one rounding each), i.e. tn <= tf (1 + 2^-19 + 2u + ...) <= fl(tf * kBoxPos).
-template <bool MAIN, bool TPOS>
+template <bool MAIN, bool TPOS, bool ANY = false>
 __device__ bool cbvh_walk_t(const TraceParams& P, uint4 hd, d3 o, d3 d, double tm, int frame,
                           double tmin, double tmax, double& t_out, uint32_t& hit_node,
                           int& hit_frame, bool& flag) {
@@ -1766,6 +1821,9 @@ __device__ bool cbvh_walk_t(const TraceParams& P, uint4 hd, d3 o, d3 d, double t
 #ifdef RT_PROF
     pf_leaf_cyc += __builtin_readcyclecounter() - pf_l0;
 #endif
+    if constexpr (ANY) {
+      if (hit) break;
+    }
     ref = pop();
   }
   flag = ((second < kInf) & (second <= closest * (1.0 + 3.0 * kTieRel))) |
@@ -1804,17 +1862,17 @@ __device__ bool cbvh_walk_t(const TraceParams& P, uint4 hd, d3 o, d3 d, double t
   }
   return hit;
 }
-template <bool MAIN>
+template <bool MAIN, bool ANY = false>
 __device__ __forceinline__ bool cbvh_walk(const TraceParams& P, uint4 hd, d3 o, d3 d, double tm,
                                           int frame, double tmin, double tmax, double& t_out,
                                           uint32_t& hit_node, int& hit_frame, bool& flag) {
-  return tmin >= 0.0 ? cbvh_walk_t<MAIN, true>(P, hd, o, d, tm, frame, tmin, tmax, t_out,
-                                               hit_node, hit_frame, flag)
-                     : cbvh_walk_t<MAIN, false>(P, hd, o, d, tm, frame, tmin, tmax, t_out,
-                                                hit_node, hit_frame, flag);
+  return tmin >= 0.0 ? cbvh_walk_t<MAIN, true, ANY>(P, hd, o, d, tm, frame, tmin, tmax, t_out,
+                                                    hit_node, hit_frame, flag)
+                     : cbvh_walk_t<MAIN, false, ANY>(P, hd, o, d, tm, frame, tmin, tmax, t_out,
+                                                     hit_node, hit_frame, flag);
 }
 
-template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK>
+template <bool MAIN, bool COUNT, bool VOLB, bool BVH, bool PK, bool ANY>
 __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, uint32_t obvh,
                             d3 wo, d3 wd, double tm, d3 o, d3 d, int frame, double tmin,
                             double tmax, double& t_out, uint32_t& hit_node, int& hit_frame,
@@ -1841,17 +1899,18 @@ __device__ bool bvh_subtree(const TraceParams& P, uint32_t node, uint32_t stop, 
       const uint4 hd = ld4u((gptr)P.nodes + obvh);  // [n_entries][cbvh block][root ref][streams]
       bool h;
       if (P.cbvh_lds_off != ~0u && hd.y != ~0u)  // the compact copy in LDS
-        h = cbvh_walk<MAIN>(P, hd, o, d, tm, frame, tmin, tmax, t_out, hit_node, hit_frame, flag);
+        h = cbvh_walk<MAIN, ANY>(P, hd, o, d, tm, frame, tmin, tmax, t_out, hit_node, hit_frame,
+                                 flag);
       else
-        h = obvh_walk<MAIN>(P, obvh, o, d, tm, frame, tmin, tmax, t_out, hit_node, hit_frame,
-                            flag);
+        h = obvh_walk<MAIN, ANY>(P, obvh, o, d, tm, frame, tmin, tmax, t_out, hit_node, hit_frame,
+                                 flag);
       if (__ballot(flag) != 0ull && flag)  // rare: the reference order decides
-        h = traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK>(
+        h = traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK, ANY>(
             P, node, stop, wo, wd, tm, o, d, frame, tmin, tmax, t_out, hit_node, hit_frame, g, C);
       return h;
     }
   }
-  return traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK>(
+  return traverse<MAIN, COUNT, VOLB, false, BVH, VOLB, true, 0, PK, ANY>(
       P, node, stop, wo, wd, tm, o, d, frame, tmin, tmax, t_out, hit_node, hit_frame, g, C);
 }
 

@@ -15,6 +15,12 @@
 //
 // The launch runs on the AOV pass's LDS plan at the plan's workgroup size (rt_aov.h): the same
 // prologue, the same five instances.
+//
+// ANY (mode RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT): five more instances whose world query is the
+// walker's ANY form (rt_kernel.h traverse): it leaves at the first accept and returns the closest-
+// hit walk's flag. A tail lane and a lane with an invalid ray enter it with the empty interval
+// [1, 0], so they are done from the start: their fixed ray misses most scenes and would hold every
+// ragged or partly invalid wave to the full walk.
 #pragma once
 #include "rt_kernel.h"
 
@@ -37,7 +43,7 @@ __device__ __forceinline__ int prim_of(const uint32_t* __restrict__ prim_tab, ui
   return lo < n_prim && prim_tab[lo] == hn ? (int)prim_tab[n_prim + lo] : -1;
 }
 
-template <bool BVH, bool STAGED, int VN>
+template <bool BVH, bool STAGED, int VN, bool ANY = false>
 __device__ __forceinline__ void query_body(const TraceParams& P, const uint4* __restrict__ rays,
                                            void* __restrict__ out, uint32_t n_rays, uint32_t mode,
                                            const uint32_t* __restrict__ prim_tab, uint32_t n_prim) {
@@ -65,6 +71,7 @@ __device__ __forceinline__ void query_body(const TraceParams& P, const uint4* __
   const bool ok = live && valid && tmax_in == tmax_in;
   d3 ro = mk(0., 0., 0.), rd = mk(0., 0., 1.);
   double tm = 0.0, tmin = 0.0001, tmax = kInf;
+  if constexpr (ANY) tmin = 1.0, tmax = 0.0;  // done at entry unless the lane has a ray
   uint32_t pixel = 0u, sample = 0u;
   if (ok) {
     ro = mk(hilo(r0.x, r0.y), hilo(r0.z, r0.w), hilo(r1.x, r1.y));
@@ -82,10 +89,10 @@ __device__ __forceinline__ void query_body(const TraceParams& P, const uint4* __
   double t;
   uint32_t hn = 0;
   int hf = -1;
-  const bool hit_w = traverse<true, COUNT, true, true, BVH, true, true, VN, true>(
+  const bool hit_w = traverse<true, COUNT, true, true, BVH, true, true, VN, true, ANY>(
       P, P.root, ~0u, ro, rd, tm, ro, rd, -1, tmin, tmax, t, hn, hf, g, C);
   if (!live) return;
-  if (mode & RT_QUERY_OCCLUSION) {
+  if (ANY || (mode & RT_QUERY_OCCLUSION)) {  // ANY has no record to fill (the host checks mode)
     reinterpret_cast<uint8_t*>(out)[i] = ok ? (hit_w ? (uint8_t)1 : (uint8_t)0) : (uint8_t)255;
     return;
   }

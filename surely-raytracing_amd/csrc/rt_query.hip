@@ -27,21 +27,27 @@ namespace {
 // The AOV pass's five instances (rt_aov.hip): BVH (per-lane walker, the plan's 768-thread
 // workgroup), STAGED (table reads from the LDS copy), VN (nested volumes); every feature bit set.
 // TraceParams stays the first argument, as in every kernel on this plan; the query's walker is
-// instantiated with PK and reads nothing through kparams() (rt_query.h).
-template <bool BVH, bool STAGED, int VN>
+// instantiated with PK and reads nothing through kparams() (rt_query.h). ANY: the five any-hit
+// instances, the same plan, workgroup and prologue.
+template <bool BVH, bool STAGED, int VN, bool ANY = false>
 __global__ __launch_bounds__(BlockOf<BVH>::value) void rt_query(
     TraceParams P, const uint4* __restrict__ rays, void* __restrict__ out, uint32_t n_rays,
     uint32_t mode, const uint32_t* __restrict__ prim_tab, uint32_t n_prim) {
-  query_body<BVH, STAGED, VN>(P, rays, out, n_rays, mode, prim_tab, n_prim);
+  query_body<BVH, STAGED, VN, ANY>(P, rays, out, n_rays, mode, prim_tab, n_prim);
 }
 
 typedef void (*query_kern_t)(TraceParams, const uint4*, void*, uint32_t, uint32_t, const uint32_t*,
                              uint32_t);
-query_kern_t query_kernel(const rtv::Variant& v) {
+template <bool ANY>
+query_kern_t query_kernel_of(const rtv::Variant& v) {
   if (v.vn)
-    return v.bvh ? rt_query<true, false, RTL_VOLUME_NEST> : rt_query<false, false, RTL_VOLUME_NEST>;
-  if (v.staged) return rt_query<false, true, 0>;
-  return v.bvh ? rt_query<true, false, 0> : rt_query<false, false, 0>;
+    return v.bvh ? rt_query<true, false, RTL_VOLUME_NEST, ANY>
+                 : rt_query<false, false, RTL_VOLUME_NEST, ANY>;
+  if (v.staged) return rt_query<false, true, 0, ANY>;
+  return v.bvh ? rt_query<true, false, 0, ANY> : rt_query<false, false, 0, ANY>;
+}
+query_kern_t query_kernel(const rtv::Variant& v, uint32_t mode) {
+  return (mode & RT_QUERY_ANY_HIT) ? query_kernel_of<true>(v) : query_kernel_of<false>(v);
 }
 
 // made before the scene is read and before any HIP call
@@ -51,7 +57,10 @@ int check_query_args(const rt_scene* sc, const rt_query_params* qp, const void* 
   if (n_rays >= (1ull << 31)) return set_err(RT_ERR_INVALID_ARG, "n_rays >= 2^31");
   if (qp->flags & ~RT_FLAG_REFERENCE_BVH)
     return set_err(RT_ERR_INVALID_ARG, "ray queries take RT_FLAG_REFERENCE_BVH only");
-  if (qp->mode & ~RT_QUERY_OCCLUSION) return set_err(RT_ERR_INVALID_ARG, "unknown query mode bits");
+  if (qp->mode & ~(RT_QUERY_OCCLUSION | RT_QUERY_ANY_HIT))
+    return set_err(RT_ERR_INVALID_ARG, "unknown query mode bits");
+  if ((qp->mode & RT_QUERY_ANY_HIT) && !(qp->mode & RT_QUERY_OCCLUSION))
+    return set_err(RT_ERR_INVALID_ARG, "RT_QUERY_ANY_HIT needs RT_QUERY_OCCLUSION");
   if ((uintptr_t)rays % 16u) return set_err(RT_ERR_INVALID_ARG, "rays not 16-byte aligned");
   if (!(qp->mode & RT_QUERY_OCCLUSION) && (uintptr_t)out % 16u)
     return set_err(RT_ERR_INVALID_ARG, "out not 16-byte aligned");
@@ -104,7 +113,7 @@ int rt_query_rays_device(rt_scene* sc, const rt_query_params* qp, const rt_ray* 
   fill_trace_params(&P, sc, &cam, &opts, LP);
   P.sphere_light0 = -1;
   const query_kern_t kern =
-      query_kernel(rtv::choose_variant(sc->hdr, qp->flags, LP.stage_scene != 0));
+      query_kernel(rtv::choose_variant(sc->hdr, qp->flags, LP.stage_scene != 0), qp->mode);
   if (LP.lds_bytes > (64u << 10))
     HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)LP.lds_bytes));

@@ -161,6 +161,11 @@ class RtRaysParams(C.Structure):
                 ("background", C.c_double * 3)]
 
 
+class RthAoParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("radius", C.c_double), ("tmin", C.c_double),
+                ("dir_index", C.c_uint32), ("_pad0", C.c_uint32)]
+
+
 class RthProjection(C.Structure):
     _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("sqrt_spp", C.c_int32), ("origin", C.c_double * 3),
@@ -177,6 +182,7 @@ PROJECTIONS = {"pinhole": RTH_PROJ_PINHOLE, "ortho": RTH_PROJ_ORTHO,
 
 # ray queries (rt_query_rays*): numpy views of rt_ray / rt_hit, 80 bytes each
 RT_QUERY_OCCLUSION = 0x1  # out is one uint8 per ray: 1 hit, 0 miss, 255 invalid
+RT_QUERY_ANY_HIT = 0x2  # with RT_QUERY_OCCLUSION only: the same bytes, the walk leaves at its first accept
 RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("time", "<f8"), ("tmin", "<f8"),
                       ("tmax", "<f8"), ("pixel", "<u4"), ("sample", "<u4")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("distance", "<f8"), ("p", "<f8", 3), ("normal", "<f8", 3),
@@ -226,6 +232,29 @@ def projection_rays(kind, seed: int = 1, s_i: int = 0, s_j: int = 0, cam: "RtCam
     _check_host(host_lib().rth_projection_rays(C.byref(pr), C.byref(cam) if cam is not None else None,
                                                seed, s_i, s_j, rays.ctypes.data))
     return rays
+
+
+def ao_rays(rays: np.ndarray, hits: np.ndarray, k: int, seed: int = 1, radius: float = float("inf"),
+            tmin: float = 1e-4) -> np.ndarray:
+    """rth_ao_rays: the k-th ambient-occlusion batch for primary `rays` (RAY_DTYPE) and their
+    records `hits` (HIT_DTYPE, DeviceScene.query): per hit a cosine-distributed direction about the
+    normal over [tmin, radius], per non-hit an invalid ray. Query it with occlusion=True,
+    any_hit=True; a pixel's ambient occlusion is the share of 0 bytes over K batches."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    if len(rays) != len(hits):
+        raise ValueError("ao_rays: rays and hits differ in length")
+    out = np.zeros(len(rays), RAY_DTYPE)
+    if not len(rays):
+        return out
+    ap = RthAoParams(seed, radius, tmin, k, 0)
+    _check_host(host_lib().rth_ao_rays(rays.ctypes.data, hits.ctypes.data, len(rays), C.byref(ap),
+                                       out.ctypes.data))
+    return out
+
+
+def _query_mode(occlusion: bool, any_hit: bool) -> int:
+    return (RT_QUERY_OCCLUSION if occlusion else 0) | (RT_QUERY_ANY_HIT if any_hit else 0)
 
 
 class RtError(RuntimeError):
@@ -297,6 +326,8 @@ def host_lib() -> C.CDLL:
             "rth_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, i32, i32]),
             "rth_projection_rays": (C.c_int, [C.POINTER(RthProjection), C.POINTER(RtCamera),
                                               C.c_uint64, i32, i32, C.c_void_p]),
+            "rth_ao_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RthAoParams),
+                                      C.c_void_p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -772,14 +803,15 @@ class DeviceScene:
         return st
 
     def query(self, rays: np.ndarray, seed: int = 1, flags: int = 0, occlusion: bool = False,
-              stats: bool = False):
+              stats: bool = False, any_hit: bool = False):
         """Synchronous rt_query_rays: the closest hit of every ray of a RAY_DTYPE array
         (make_rays) as a HIT_DTYPE array, or with occlusion=True one uint8 per ray (1 hit, 0 miss,
-        255 invalid ray). `flags`: RT_FLAG_REFERENCE_BVH or 0. Returns the array, or (array, stats)
-        with stats=True."""
+        255 invalid ray). any_hit=True (with occlusion=True only): the same bytes from a walk that
+        leaves at the first accepted primitive. `flags`: RT_FLAG_REFERENCE_BVH or 0. Returns the
+        array, or (array, stats) with stats=True."""
         rays = np.ascontiguousarray(rays, RAY_DTYPE)
         out = np.zeros(len(rays), np.uint8 if occlusion else HIT_DTYPE)
-        qp = RtQueryParams(seed, flags, RT_QUERY_OCCLUSION if occlusion else 0)
+        qp = RtQueryParams(seed, flags, _query_mode(occlusion, any_hit))
         st = RtStats()
         if len(rays):
             _check_dev(self._lib.rt_query_rays(self._h, C.byref(qp), rays.ctypes.data, len(rays),
@@ -787,11 +819,13 @@ class DeviceScene:
         return (out, st) if stats else out
 
     def query_device(self, rays_ptr: int, n: int, out_ptr: int, seed: int = 1, flags: int = 0,
-                     occlusion: bool = False, stream: int = 0, stats: bool = False):
+                     occlusion: bool = False, stream: int = 0, stats: bool = False,
+                     any_hit: bool = False):
         """Asynchronous rt_query_rays_device: n rt_ray records at rays_ptr (16-byte aligned, e.g. a
-        torch tensor's data_ptr()) into n rt_hit records, or n bytes with occlusion=True, at
-        out_ptr, on `stream` (e.g. torch.cuda.current_stream().cuda_stream)."""
-        qp = RtQueryParams(seed, flags, RT_QUERY_OCCLUSION if occlusion else 0)
+        torch tensor's data_ptr()) into n rt_hit records, or n bytes with occlusion=True (any_hit=
+        True: the early-exit walk, the same bytes), at out_ptr, on `stream` (e.g.
+        torch.cuda.current_stream().cuda_stream)."""
+        qp = RtQueryParams(seed, flags, _query_mode(occlusion, any_hit))
         st = RtStats() if stats else None
         _check_dev(self._lib.rt_query_rays_device(
             self._h, C.byref(qp), C.c_void_p(rays_ptr), n, C.c_void_p(out_ptr),

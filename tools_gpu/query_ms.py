@@ -1,4 +1,4 @@
-"""Device time of the ray query (rt_query_rays_device) in record and in occlusion mode, next to the
+"""Device time of the ray query (rt_query_rays_device) in record, occlusion and any-hit mode, next to the
 first-hit AOV pass (rt_render_aov_device) for the same count of rays: the frame's W x H x SPP
 camera rays, built on the host from the preset's camera at fixed stratum centres (no random jitter,
 no defocus, time 0; the AOV pass jitters its own, so the two trace the same pixels' cones, not the
@@ -7,6 +7,13 @@ another, 64 consecutive rays per tile and sample (or, with `sample`, a whole fra
 Per step: one warm-up, then the median (and minimum) ms_kernel over ROUNDS calls; Grays/s; bytes
 moved over kernel time (160 B per ray in record mode, 81 B in occlusion mode) and their share of
 the HBM peak (surely_rt.roofline.PEAK_HBM_GBPS).
+
+Any-hit (RT_QUERY_ANY_HIT): step `anyhit` runs the camera rays of `occlusion`; the ray set `ao` has
+its origins at those camera rays' first hits (one record query) and one cosine-distributed direction
+each (surely_rt.ao_rays, every ray its own stream), once with radius = inf and once with a finite
+radius of a tenth of the scene's bounding-box diagonal, each timed in occlusion and in any-hit
+mode (steps ao_inf_occlusion, ao_inf_anyhit, ao_r_occlusion, ao_r_anyhit). Rays that saw no
+surface are invalid rays there (byte 255); the line gives the counts of 1, 0 and 255 bytes.
 
 Every step runs in a process of its own under its own `timeout`, chained with `&&`: a step that
 fails or hangs ends the chain.
@@ -17,7 +24,8 @@ import sys
 sys.path.insert(0, "surely-raytracing_amd")
 sys.path.insert(0, "tests")
 
-STEPS = ("record", "occlusion", "aov")
+STEPS = ("record", "occlusion", "anyhit", "aov", "ao_inf_occlusion", "ao_inf_anyhit",
+         "ao_r_occlusion", "ao_r_anyhit")
 
 
 def camera_rays(rt, np, cam, order="tile"):
@@ -52,7 +60,9 @@ def step(name, scene, W, SPP, rounds, order):
     from hip_buf import DevBuf
     from surely_rt.roofline import PEAK_HBM_GBPS
 
-    blob, cam = rt.preset_blob(scene, width=W, spp=SPP)
+    host = rt.Scene(1)
+    world, lights, cam = host.preset(scene, width=W, spp=SPP)
+    blob = host.serialize(world, lights)
     H = cam.image_height
     ds = rt.DeviceScene(blob)
     n = W * H * cam.samples_per_pixel
@@ -66,11 +76,20 @@ def step(name, scene, W, SPP, rounds, order):
     else:
         rays = camera_rays(rt, np, cam, order)
         assert len(rays) == n
-        occ = name == "occlusion"
+        occ = name != "record"
+        any_hit = name.endswith("anyhit")
+        if name.startswith("ao_"):
+            hits = ds.query(rays, seed=1)
+            bb = host.bbox(world)  # x, y, z (min, max) pairs
+            radius = float("inf") if name.startswith("ao_inf") else 0.1 * float(np.linalg.norm(bb[1::2] - bb[0::2]))
+            rays["pixel"] = np.arange(n, dtype=np.uint32)  # every ray its own stream
+            rays = rt.ao_rays(rays, hits, 0, seed=1, radius=radius)
+            del hits
         d_in = DevBuf((n, 20), init=rays.view(np.uint8).reshape(n, 80).view(np.float32))
         out = DevBuf((n, 20) if not occ else ((n + 3) // 4,))
         bufs = [d_in, out]
-        run = lambda: ds.query_device(d_in.ptr, n, out.ptr, seed=1, occlusion=occ, stats=True)  # noqa: E731
+        run = lambda: ds.query_device(d_in.ptr, n, out.ptr, seed=1, occlusion=occ, any_hit=any_hit,  # noqa: E731
+                                      stats=True)
         per_ray = 81 if occ else 160
     run()
     ms = [run().ms_kernel for _ in range(rounds)]
@@ -84,6 +103,11 @@ def step(name, scene, W, SPP, rounds, order):
         if not occ:
             h = out.download().view(np.uint8).reshape(n, 80).view(rt.HIT_DTYPE).ravel()
             line += f"  ({int((h['hit'] == 1).sum())} hits)"
+        else:
+            b = out.download().view(np.uint8).ravel()[:n]
+            line += f"  (bytes 1/0/255: {int((b == 1).sum())}/{int((b == 0).sum())}/{int((b == 255).sum())})"
+            if name.startswith("ao_r"):
+                line += f"  radius {radius:.4g}"
     print(line, flush=True)
     for b in bufs:
         b.free()
