@@ -19,7 +19,7 @@ CFLAGS_O := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unuse
 
 HOST_SRC := $(CSRC)/host/scene.cpp $(CSRC)/host/presets.cpp $(CSRC)/host/capi.cpp
 DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_rays.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
-DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
+DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_stage.hpp $(CSRC)/rt_pass.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
 .PHONY: all device host oracle cli gather checks probe clean

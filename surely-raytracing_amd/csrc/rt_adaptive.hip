@@ -4,30 +4,23 @@
 // translation unit; of scenes it knows only the C ABI.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
 #include "rt_mi355x.h"
-#include "rt_scene_impl.hpp"  // set_err, HIP_TRY
+#include "rt_stage.hpp"
 
 using rts::set_err;
+using rts::time_point;
 
-// One workspace and one ordering event per handle. `mu` serialises the calls; a call's stream
-// waits for `done` of the call before it, and the host copy of rows_held that an asynchronous
-// resolve uploads from is rewritten only after `done`.
-struct rt_adaptive {
-  int device = 0;
-  uint8_t* work = nullptr;  // per tile: rows_held (u32), error (f32), invalid pixels (u32)
-  size_t work_tiles = 0;
+// The workspace holds, per tile, rows_held (u32), the error (f32) and the invalid pixels (u32).
+// The host copy of rows_held that an asynchronous resolve uploads from is rewritten only after
+// `done`. Not timed: the driver's stats are the renders'.
+struct rt_adaptive : rts::Stage {
   std::vector<uint32_t> rows_host;
   std::vector<uint32_t> back;  // the error and invalid counts as downloaded
-  hipEvent_t done = nullptr;
-  bool recorded = false;
-  std::mutex mu;
 };
 
 namespace {
@@ -101,11 +94,6 @@ __global__ __launch_bounds__(256) void ad_resolve(const float* accum,
   if (samples) samples[p] = (float)B;
 }
 
-typedef std::chrono::steady_clock::time_point time_point;
-double ms_since(time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int check_frame(int width, int height, int sqrt_spp) {
   if (width <= 0 || height < 0)
     return set_err(RT_ERR_INVALID_ARG, "bad frame size (width <= 0 or height < 0)");
@@ -127,33 +115,16 @@ size_t tile_count(int width, int height) {
 }
 
 // rows_held into the handle's host copy and workspace (ad->mu held): both may still be in use by
-// the handle's previous call, which `done` follows
+// the handle's previous call, which `done` follows. The wait for it is the host's, not the
+// stream's (so the callers' Run needs no begin()): the host vector is reused.
 int upload_rows(rt_adaptive* ad, const uint32_t* rows, size_t n_tiles, hipStream_t stream) {
   HIP_TRY(hipSetDevice(ad->device));
   if (ad->recorded) HIP_TRY(hipEventSynchronize(ad->done));
-  if (n_tiles > ad->work_tiles) {
-    if (ad->work) HIP_TRY(hipFree(ad->work));
-    ad->work = nullptr;
-    ad->work_tiles = 0;
-    HIP_TRY(hipMalloc((void**)&ad->work, n_tiles * 12));
-    ad->work_tiles = n_tiles;
-  }
+  RT_TRY(ad->reserve(n_tiles * 12));
   ad->rows_host.assign(rows, rows + n_tiles);
   HIP_TRY(hipMemcpyAsync(ad->work, ad->rows_host.data(), n_tiles * 4, hipMemcpyHostToDevice, stream));
   return RT_OK;
 }
-
-// records `done` after whatever the call enqueued, on every exit path
-struct DoneGuard {
-  rt_adaptive* ad;
-  hipStream_t stream;
-  ~DoneGuard() {
-    if (hipEventRecord(ad->done, stream) == hipSuccess)
-      ad->recorded = true;
-    else
-      (void)hipStreamSynchronize(stream);
-  }
-};
 
 // rt_adaptive_tile_error with the arguments checked and ad->mu held
 int tile_error_locked(rt_adaptive* ad, int W, int H, int S, double floor, const float* accum,
@@ -165,7 +136,7 @@ int tile_error_locked(rt_adaptive* ad, int W, int H, int S, double floor, const 
   const int rc = upload_rows(ad, rows, n_tiles, stream);
   if (rc != RT_OK) return rc;
   {
-    DoneGuard guard{ad, stream};
+    rts::Run run(*ad, stream);
     uint32_t* d_rows = reinterpret_cast<uint32_t*>(ad->work);
     float* d_err = reinterpret_cast<float*>(ad->work + n_tiles * 4);
     uint32_t* d_inv = reinterpret_cast<uint32_t*>(ad->work + n_tiles * 8);
@@ -191,7 +162,7 @@ int resolve_locked(rt_adaptive* ad, int W, int H, int S, const uint32_t* rows, c
   if (n_tiles == 0) return RT_OK;
   const int rc = upload_rows(ad, rows, n_tiles, stream);
   if (rc != RT_OK) return rc;
-  DoneGuard guard{ad, stream};
+  rts::Run run(*ad, stream);
   const size_t n_px = (size_t)W * H;
   hipLaunchKernelGGL(ad_resolve, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, accum,
                      reinterpret_cast<const uint32_t*>(ad->work), out, samples, W, H,
@@ -216,35 +187,10 @@ int rt_adaptive_schedule(int sqrt_spp, int passes, int pass, int* sj_begin, int*
 }
 
 int rt_adaptive_create(int device, rt_adaptive** out) {
-  if (!out) return set_err(RT_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_err(RT_ERR_NO_DEVICE, "no HIP device available");
-  if (device < 0 || device >= ndev) return set_err(RT_ERR_INVALID_ARG, "bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-  rt_adaptive* ad = new rt_adaptive;
-  ad->device = device;
-  const hipError_t e = hipEventCreateWithFlags(&ad->done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    rt_adaptive_destroy(ad);
-    return set_err(RT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = ad;
-  return RT_OK;
+  return rts::stage_create(device, false, out);
 }
 
-void rt_adaptive_destroy(rt_adaptive* ad) {
-  if (!ad) return;
-  {
-    std::lock_guard<std::mutex> lock(ad->mu);
-    (void)hipSetDevice(ad->device);
-    if (ad->recorded) (void)hipEventSynchronize(ad->done);
-    if (ad->work) (void)hipFree(ad->work);
-    if (ad->done) (void)hipEventDestroy(ad->done);
-  }
-  delete ad;
-}
+void rt_adaptive_destroy(rt_adaptive* ad) { rts::stage_destroy(ad); }
 
 int rt_adaptive_tile_error(rt_adaptive* ad, int width, int height, int sqrt_spp, double floor,
                            const float* accum, const float* m2, const uint32_t* rows_held,
@@ -342,7 +288,7 @@ int rt_render_adaptive_device(rt_adaptive* ad, rt_scene* sc, const rt_camera* ca
   }
   if (rows_held_out) std::memcpy(rows_held_out, held.data(), n_tiles * sizeof(uint32_t));
   if (stats) {
-    sum.ms_total = ms_since(t0);
+    sum.ms_total = rts::ms_since(t0);
     *stats = sum;
   }
   return RT_OK;
@@ -358,28 +304,21 @@ int rt_render_adaptive(rt_adaptive* ad, rt_scene* sc, const rt_camera* cam,
   if (cam->image_width <= 0 || opts->n_rows < 0) return set_err(RT_ERR_INVALID_ARG, "bad size");
   if (samples && !out) return set_err(RT_ERR_INVALID_ARG, "adaptive: samples needs out");
   const size_t n_px = (size_t)cam->image_width * (size_t)opts->n_rows;
-  HIP_TRY(hipSetDevice(ad->device));
-  // one allocation: the sums, the second moments, the resolved frame, the sample counts
+  // the sums, the second moments, the resolved frame, the sample counts
   const size_t b3 = n_px * 3 * sizeof(float);
-  uint8_t* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 3 * b3 + n_px * sizeof(float) + 16));
-  float* const d_acc = reinterpret_cast<float*>(d);
-  float* const d_m2 = reinterpret_cast<float*>(d + b3);
-  float* const d_out = out ? reinterpret_cast<float*>(d + 2 * b3) : nullptr;
-  float* const d_smp = samples ? reinterpret_cast<float*>(d + 3 * b3) : nullptr;
-  int rc = rt_render_adaptive_device(ad, sc, cam, opts, ap, d_acc, d_m2, d_out, d_smp,
-                                     rows_held_out, tiles_per_pass, nullptr, stats);
-  if (rc == RT_OK && n_px) {
-    hipError_t e = hipMemcpy(accum, d_acc, b3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(m2, d_m2, b3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out) e = hipMemcpy(out, d_out, b3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && samples)
-      e = hipMemcpy(samples, d_smp, n_px * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(d);
-  if (rc == RT_OK && stats) stats->ms_total = ms_since(t0);
-  return rc;
+  rts::Staging st;
+  const int i_acc = st.add(b3), i_m2 = st.add(b3), i_out = st.add_if(out != nullptr, b3);
+  const int i_smp = st.add_if(samples != nullptr, n_px * sizeof(float));
+  RT_TRY(st.alloc(ad->device));
+  RT_TRY(rt_render_adaptive_device(ad, sc, cam, opts, ap, st.ptr<float>(i_acc), st.ptr<float>(i_m2),
+                                   st.ptr<float>(i_out), st.ptr<float>(i_smp), rows_held_out,
+                                   tiles_per_pass, nullptr, stats));
+  RT_TRY(st.download(i_acc, accum));
+  RT_TRY(st.download(i_m2, m2));
+  RT_TRY(st.download(i_out, out));
+  RT_TRY(st.download(i_smp, samples));
+  if (stats) stats->ms_total = rts::ms_since(t0);
+  return RT_OK;
 }
 
 }  // extern "C"

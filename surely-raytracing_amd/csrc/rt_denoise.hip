@@ -3,31 +3,20 @@
 // Its own translation unit, built beside rt_device.hip and rt_aov.hip; it knows nothing of scenes.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <utility>
 
 #include "rt_mi355x.h"
 #include "rt_denoise.h"
-#include "rt_scene_impl.hpp"  // set_err, HIP_TRY
+#include "rt_stage.hpp"
 
 using namespace rtd;
 using rts::set_err;
+using rts::time_point;
 
-// One workspace and one ordering event per handle. `mu` serialises the calls; every call's stream
-// waits for `done` of the call before it (whatever stream that went to), so the workspace is never
-// shared by two calls in flight.
-struct rt_denoiser {
-  int device = 0;
-  uint8_t* work = nullptr;
-  size_t work_bytes = 0;
-  hipEvent_t done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool recorded = false;  // `done` has been recorded at least once
-  std::mutex mu;
-};
+struct rt_denoiser : rts::Stage {};
 
 namespace {
 
@@ -131,26 +120,6 @@ float term_scale(double sigma) {
   return sigma > 0.0 ? (float)(1.4426950408889634 / (sigma * sigma)) : 0.f;
 }
 
-// Records `done` after whatever a failing call has enqueued, so that the next call still waits
-// for the kernels that may be using the workspace.
-struct DoneGuard {
-  rt_denoiser* dn;
-  hipStream_t stream;
-  bool enqueued = false, finished = false;
-  ~DoneGuard() {
-    if (!enqueued || finished) return;
-    if (hipEventRecord(dn->done, stream) == hipSuccess)
-      dn->recorded = true;
-    else
-      (void)hipStreamSynchronize(stream);
-  }
-};
-
-typedef std::chrono::steady_clock::time_point time_point;
-double ms_since(time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // Both filters on device buffers, the arguments already checked. A null m2 is the plain filter
 // (var_out null, beauty_rows unused); otherwise the variance-guided one.
 int denoise_device(rt_denoiser* dn, const Fields& f, int beauty_rows, const float* beauty,
@@ -167,17 +136,7 @@ int denoise_device(rt_denoiser* dn, const Fields& f, int beauty_rows, const floa
   // bytes of workspace per pixel: G0, G1 and the two colour records the levels alternate between
   // (a single plain level reads one and writes the user's buffer; the prefilter always writes the
   // second)
-  const size_t need = n_px * (var || f.levels > 1 ? 64 : 48);
-  if (need > dn->work_bytes) {
-    // the previous call may still be reading the old workspace
-    if (dn->recorded) HIP_TRY(hipEventSynchronize(dn->done));
-    if (dn->work) HIP_TRY(hipFree(dn->work));
-    dn->work = nullptr;
-    dn->work_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&dn->work, need));
-    dn->work_bytes = need;
-  }
-  if (dn->recorded) HIP_TRY(hipStreamWaitEvent(stream, dn->done, 0));
+  RT_TRY(dn->reserve(n_px * (var || f.levels > 1 ? 64 : 48)));
   float4* const G0 = reinterpret_cast<float4*>(dn->work);
   float4* const G1 = G0 + n_px;
   float4 *xin = G1 + n_px, *xout = xin + n_px;  // xout: touched only at 64 B per pixel
@@ -196,45 +155,38 @@ int denoise_device(rt_denoiser* dn, const Fields& f, int beauty_rows, const floa
   const unsigned tiles_x = ((unsigned)P.W + kTileW - 1) / kTileW;
   const unsigned tiles_y = ((unsigned)P.H + kTileH - 1) / kTileH;
   const dim3 grid(tiles_x * tiles_y), block(kBlock);  // W * H < 2^31: fewer than 2^28 + W + H tiles
-  DoneGuard guard{dn, stream};
-  guard.enqueued = true;
-  if (stats) HIP_TRY(hipEventRecord(dn->ev0, stream));
-  if (var) {
-    P.k_color = term_scale(f.sigma_color);  // every level: the propagated variance narrows it
-    V.n = (double)beauty_rows;
-    V.vscale = V.n / ((V.n - 1.0) * f.beauty_samples * f.beauty_samples);
-    hipLaunchKernelGGL(dn_prepare_var, grid, block, 0, stream, V, beauty, m2, aov, G0, G1, xin);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dn_prefilter_var, grid, block, 0, stream, P, G1, xin, xout);
-    HIP_TRY(hipGetLastError());
-    std::swap(xin, xout);
-  } else {
-    hipLaunchKernelGGL(dn_prepare, grid, block, 0, stream, P, beauty, aov, G0, G1, xin);
-    HIP_TRY(hipGetLastError());
+  {
+    rts::Run run(*dn, stream);
+    RT_TRY(run.begin(stats != nullptr));
+    if (var) {
+      P.k_color = term_scale(f.sigma_color);  // every level: the propagated variance narrows it
+      V.n = (double)beauty_rows;
+      V.vscale = V.n / ((V.n - 1.0) * f.beauty_samples * f.beauty_samples);
+      hipLaunchKernelGGL(dn_prepare_var, grid, block, 0, stream, V, beauty, m2, aov, G0, G1, xin);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(dn_prefilter_var, grid, block, 0, stream, P, G1, xin, xout);
+      HIP_TRY(hipGetLastError());
+      std::swap(xin, xout);
+    } else {
+      hipLaunchKernelGGL(dn_prepare, grid, block, 0, stream, P, beauty, aov, G0, G1, xin);
+      HIP_TRY(hipGetLastError());
+    }
+    for (int k = 0; k < f.levels; ++k) {
+      P.step = 1 << k;
+      if (!var) P.k_color = term_scale((double)f.sigma_color / (double)(1 << k));  // sigma_c * 2^-k
+      const bool last = k + 1 == f.levels;
+      const level_kern_t kern = var ? level_kernel<true>(k, last) : level_kernel<false>(k, last);
+      hipLaunchKernelGGL(kern, grid, block, 0, stream, P, G0, G1, xin, xout, beauty, aov, out,
+                         var_out);
+      HIP_TRY(hipGetLastError());
+      std::swap(xin, xout);
+    }
+    if (stats) HIP_TRY(hipEventRecord(dn->ev1, stream));
   }
-  for (int k = 0; k < f.levels; ++k) {
-    P.step = 1 << k;
-    if (!var) P.k_color = term_scale((double)f.sigma_color / (double)(1 << k));  // sigma_c * 2^-k
-    const bool last = k + 1 == f.levels;
-    const level_kern_t kern = var ? level_kernel<true>(k, last) : level_kernel<false>(k, last);
-    hipLaunchKernelGGL(kern, grid, block, 0, stream, P, G0, G1, xin, xout, beauty, aov, out,
-                       var_out);
-    HIP_TRY(hipGetLastError());
-    std::swap(xin, xout);
-  }
-  if (stats) HIP_TRY(hipEventRecord(dn->ev1, stream));
-  HIP_TRY(hipEventRecord(dn->done, stream));
-  dn->recorded = true;
-  guard.finished = true;
   if (stats) {
-    HIP_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, dn->ev0, dn->ev1));
-    stats->ms_kernel = ms;
-    stats->samples = n_px;
-    stats->out_bytes = (uint64_t)n_px * (var_out ? 4 : 3) * sizeof(float);
-    stats->launches = (var ? 2u : 1u) + (uint32_t)f.levels;
-    stats->ms_total = ms_since(t0);
+    const uint64_t out_bytes = (uint64_t)n_px * (var_out ? 4 : 3) * sizeof(float);
+    RT_TRY(dn->finish_stats(stream, stats, n_px, out_bytes, (var ? 2u : 1u) + (uint32_t)f.levels,
+                            t0));
   }
   return RT_OK;
 }
@@ -247,33 +199,22 @@ int denoise_host(rt_denoiser* dn, const Fields& f, int beauty_rows, const float*
   const size_t n_px = (size_t)f.width * (size_t)f.height;
   if (n_px == 0) return RT_OK;
   const size_t b_bytes = n_px * 3 * sizeof(float), a_bytes = n_px * RT_AOV_CHANNELS * sizeof(float);
-  const size_t m_bytes = m2 ? b_bytes : 0, v_bytes = var_out ? n_px * sizeof(float) : 0;
-  HIP_TRY(hipSetDevice(dn->device));
-  // one allocation: the beauty frame (denoised in place), the moments, the AOVs, the variance
-  uint8_t* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, b_bytes + m_bytes + a_bytes + v_bytes));
-  float* const d_beauty = reinterpret_cast<float*>(d);
-  float* const d_m2 = m2 ? reinterpret_cast<float*>(d + b_bytes) : nullptr;
-  float* const d_aov = reinterpret_cast<float*>(d + b_bytes + m_bytes);
-  float* const d_var =
-      var_out ? reinterpret_cast<float*>(d + b_bytes + m_bytes + a_bytes) : nullptr;
-  int rc = RT_OK;
-  hipError_t e = hipMemcpy(d_beauty, beauty, b_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess && m2) e = hipMemcpy(d_m2, m2, m_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_aov, aov, a_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+  // the beauty frame (denoised in place), the moments, the AOVs, the variance
+  rts::Staging st;
+  const int i_beauty = st.add(b_bytes), i_m2 = st.add_if(m2 != nullptr, b_bytes);
+  const int i_aov = st.add(a_bytes), i_var = st.add_if(var_out != nullptr, n_px * sizeof(float));
+  RT_TRY(st.alloc(dn->device));
+  RT_TRY(st.upload(i_beauty, beauty));
+  RT_TRY(st.upload(i_m2, m2));
+  RT_TRY(st.upload(i_aov, aov));
+  float* const d_beauty = st.ptr<float>(i_beauty);
   rt_stats local;
-  if (rc == RT_OK)
-    rc = denoise_device(dn, f, beauty_rows, d_beauty, d_m2, d_aov, d_beauty, d_var, nullptr,
-                        stats ? stats : &local, t0);
-  if (rc == RT_OK) {
-    e = hipMemcpy(out, d_beauty, b_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && var_out) e = hipMemcpy(var_out, d_var, v_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(d);
-  if (rc == RT_OK && stats) stats->ms_total = ms_since(t0);
-  return rc;
+  RT_TRY(denoise_device(dn, f, beauty_rows, d_beauty, st.ptr<float>(i_m2), st.ptr<float>(i_aov),
+                        d_beauty, st.ptr<float>(i_var), nullptr, stats ? stats : &local, t0));
+  RT_TRY(st.download(i_beauty, out));
+  RT_TRY(st.download(i_var, var_out));
+  if (stats) stats->ms_total = rts::ms_since(t0);
+  return RT_OK;
 }
 
 }  // namespace
@@ -302,39 +243,10 @@ int rt_denoise_default_params(int width, int height, double beauty_samples, doub
 }
 
 int rt_denoiser_create(int device, rt_denoiser** out) {
-  if (!out) return set_err(RT_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_err(RT_ERR_NO_DEVICE, "no HIP device available");
-  if (device < 0 || device >= ndev) return set_err(RT_ERR_INVALID_ARG, "bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-  rt_denoiser* dn = new rt_denoiser;
-  dn->device = device;
-  hipError_t e = hipEventCreateWithFlags(&dn->done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&dn->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&dn->ev1);
-  if (e != hipSuccess) {
-    rt_denoiser_destroy(dn);
-    return set_err(RT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = dn;
-  return RT_OK;
+  return rts::stage_create(device, true, out);
 }
 
-void rt_denoiser_destroy(rt_denoiser* dn) {
-  if (!dn) return;
-  {
-    std::lock_guard<std::mutex> lock(dn->mu);
-    (void)hipSetDevice(dn->device);
-    if (dn->recorded) (void)hipEventSynchronize(dn->done);
-    if (dn->work) (void)hipFree(dn->work);
-    if (dn->done) (void)hipEventDestroy(dn->done);
-    if (dn->ev0) (void)hipEventDestroy(dn->ev0);
-    if (dn->ev1) (void)hipEventDestroy(dn->ev1);
-  }
-  delete dn;
-}
+void rt_denoiser_destroy(rt_denoiser* dn) { rts::stage_destroy(dn); }
 
 int rt_denoise_device(rt_denoiser* dn, const rt_denoise_params* p, const float* beauty,
                       const float* aov, float* out, void* stream_v, rt_stats* stats) {

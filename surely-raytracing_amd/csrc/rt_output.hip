@@ -5,27 +5,18 @@
 // translation unit; of scenes it knows nothing.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <string>
 
 #include "rt_mi355x.h"
-#include "rt_scene_impl.hpp"  // set_err, HIP_TRY
+#include "rt_stage.hpp"
 
 using rts::set_err;
+using rts::time_point;
 
-// One workspace and one ordering event per handle, as rt_denoiser. `mu` serialises the calls; a
-// call's stream waits for `done` of the call before it.
-struct rt_output_stage {
-  int device = 0;
-  double* work = nullptr;  // [0] the exposure, [1 ..] one partial sum per reduction block
-  size_t work_blocks = 0;
-  hipEvent_t done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool recorded = false;
-  std::mutex mu;
-};
+// The workspace holds doubles: [0] the exposure, [1 ..] one partial sum per reduction block.
+struct rt_output_stage : rts::Stage {};
 
 namespace {
 
@@ -131,11 +122,6 @@ write_kern_t write_kernel(bool rgba, bool expose) {
   return expose ? out_write<3, true> : out_write<3, false>;
 }
 
-typedef std::chrono::steady_clock::time_point time_point;
-double ms_since(time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // everything that can be judged without the handle and without HIP
 int check_args(const rt_output_stage* o, const rt_output_params* p, const float* sums,
                const uint8_t* rgb8) {
@@ -154,21 +140,6 @@ int check_args(const rt_output_stage* o, const rt_output_params* p, const float*
   return RT_OK;
 }
 
-// Records `done` after whatever a failing call has enqueued, so that the next call still waits
-// for the kernels that may be using the workspace.
-struct DoneGuard {
-  rt_output_stage* o;
-  hipStream_t stream;
-  bool finished = false;
-  ~DoneGuard() {
-    if (finished) return;
-    if (hipEventRecord(o->done, stream) == hipSuccess)
-      o->recorded = true;
-    else
-      (void)hipStreamSynchronize(stream);
-  }
-};
-
 // the arguments checked, at least one pixel
 int output_device(rt_output_stage* o, const rt_output_params* p, const float* sums, uint8_t* rgb8,
                   double* exposure_out, hipStream_t stream, rt_stats* stats, time_point t0) {
@@ -181,51 +152,35 @@ int output_device(rt_output_stage* o, const rt_output_params* p, const float* su
   std::lock_guard<std::mutex> lock(o->mu);
   HIP_TRY(hipSetDevice(o->device));
   const size_t n_blocks = (n_px + kBlock * kPerLane - 1) / (kBlock * kPerLane);  // < 2^20
-  if (autoexp && n_blocks > o->work_blocks) {
-    // the previous call may still be using the old workspace
-    if (o->recorded) HIP_TRY(hipEventSynchronize(o->done));
-    if (o->work) HIP_TRY(hipFree(o->work));
-    o->work = nullptr;
-    o->work_blocks = 0;
-    HIP_TRY(hipMalloc((void**)&o->work, (n_blocks + 1) * sizeof(double)));
-    o->work_blocks = n_blocks;
-  }
-  if (o->recorded) HIP_TRY(hipStreamWaitEvent(stream, o->done, 0));
+  if (autoexp) RT_TRY(o->reserve((n_blocks + 1) * sizeof(double)));
+  double* const work = reinterpret_cast<double*>(o->work);
   double ev_host = expose && !autoexp ? p->exposure : 0.0;
   {
-    DoneGuard guard{o, stream};
-    if (stats) HIP_TRY(hipEventRecord(o->ev0, stream));
+    rts::Run run(*o, stream);
+    RT_TRY(run.begin(stats != nullptr));
     if (autoexp) {
       hipLaunchKernelGGL(out_expose_partial, dim3((unsigned)n_blocks), dim3(kBlock), 0, stream,
-                         sums, o->work + 1, n_px, 1. / (double)n_px);
+                         sums, work + 1, n_px, 1. / (double)n_px);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(out_expose_final, dim3(1), dim3(kBlock), 0, stream, o->work + 1, o->work,
+      hipLaunchKernelGGL(out_expose_final, dim3(1), dim3(kBlock), 0, stream, work + 1, work,
                          (uint32_t)n_blocks, p->samples_per_pixel * p->samples_per_pixel,
                          -std::log(0.6));
       HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(write_kernel(rgba, expose), dim3((unsigned)((n_px + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, stream, sums, rgb8, n_px, 1.0 / p->samples_per_pixel,
-                       ev_host, autoexp ? o->work : nullptr);
+                       ev_host, autoexp ? work : nullptr);
     HIP_TRY(hipGetLastError());
     if (stats) HIP_TRY(hipEventRecord(o->ev1, stream));
     if (autoexp && exposure_out)
-      HIP_TRY(hipMemcpyAsync(&ev_host, o->work, sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(o->done, stream));
-    o->recorded = true;
-    guard.finished = true;
+      HIP_TRY(hipMemcpyAsync(&ev_host, work, sizeof(double), hipMemcpyDeviceToHost, stream));
   }
-  if (stats || exposure_out) HIP_TRY(hipStreamSynchronize(stream));
+  if (stats)
+    RT_TRY(o->finish_stats(stream, stats, n_px, (uint64_t)n_px * (rgba ? 4 : 3), autoexp ? 3u : 1u,
+                           t0));
+  else if (exposure_out)
+    HIP_TRY(hipStreamSynchronize(stream));
   if (exposure_out) *exposure_out = ev_host;
-  if (stats) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, o->ev0, o->ev1));
-    stats->ms_kernel = ms;
-    stats->samples = n_px;
-    stats->out_bytes = (uint64_t)n_px * (rgba ? 4 : 3);
-    stats->launches = autoexp ? 3u : 1u;
-    stats->ms_total = ms_since(t0);
-  }
   return RT_OK;
 }
 
@@ -234,39 +189,10 @@ int output_device(rt_output_stage* o, const rt_output_params* p, const float* su
 extern "C" {
 
 int rt_output_create(int device, rt_output_stage** out) {
-  if (!out) return set_err(RT_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_err(RT_ERR_NO_DEVICE, "no HIP device available");
-  if (device < 0 || device >= ndev) return set_err(RT_ERR_INVALID_ARG, "bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-  rt_output_stage* o = new rt_output_stage;
-  o->device = device;
-  hipError_t e = hipEventCreateWithFlags(&o->done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&o->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&o->ev1);
-  if (e != hipSuccess) {
-    rt_output_destroy(o);
-    return set_err(RT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = o;
-  return RT_OK;
+  return rts::stage_create(device, true, out);
 }
 
-void rt_output_destroy(rt_output_stage* o) {
-  if (!o) return;
-  {
-    std::lock_guard<std::mutex> lock(o->mu);
-    (void)hipSetDevice(o->device);
-    if (o->recorded) (void)hipEventSynchronize(o->done);
-    if (o->work) (void)hipFree(o->work);
-    if (o->done) (void)hipEventDestroy(o->done);
-    if (o->ev0) (void)hipEventDestroy(o->ev0);
-    if (o->ev1) (void)hipEventDestroy(o->ev1);
-  }
-  delete o;
-}
+void rt_output_destroy(rt_output_stage* o) { rts::stage_destroy(o); }
 
 int rt_output_device(rt_output_stage* o, const rt_output_params* p, const float* sums, uint8_t* rgb8,
                      double* exposure_out, void* stream_v, rt_stats* stats) {
@@ -281,30 +207,23 @@ int rt_output_device(rt_output_stage* o, const rt_output_params* p, const float*
 int rt_output(rt_output_stage* o, const rt_output_params* p, const float* sums, uint8_t* rgb8,
               double* exposure_out, rt_stats* stats) {
   const time_point t0 = std::chrono::steady_clock::now();
-  int rc = check_args(o, p, sums, rgb8);
+  const int rc = check_args(o, p, sums, rgb8);
   if (rc != RT_OK) return rc;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (p->height == 0) return RT_OK;
   const size_t n_px = (size_t)p->width * (size_t)p->height;
   const size_t in_bytes = n_px * 3 * sizeof(float);
   const size_t out_bytes = n_px * ((p->flags & RT_OUTPUT_RGBA) ? 4 : 3);
-  HIP_TRY(hipSetDevice(o->device));
-  // one allocation: the sums, then the bytes (4-byte aligned: in_bytes is a multiple of 4)
-  uint8_t* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, in_bytes + out_bytes));
-  hipError_t e = hipMemcpy(d, sums, in_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+  rts::Staging st;
+  const int i_sums = st.add(in_bytes), i_rgb = st.add(out_bytes);
+  RT_TRY(st.alloc(o->device));
+  RT_TRY(st.upload(i_sums, sums));
   rt_stats local;
-  if (rc == RT_OK)
-    rc = output_device(o, p, reinterpret_cast<const float*>(d), d + in_bytes, exposure_out, nullptr,
-                       stats ? stats : &local, t0);
-  if (rc == RT_OK) {
-    e = hipMemcpy(rgb8, d + in_bytes, out_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(d);
-  if (rc == RT_OK && stats) stats->ms_total = ms_since(t0);
-  return rc;
+  RT_TRY(output_device(o, p, st.ptr<const float>(i_sums), st.ptr<uint8_t>(i_rgb), exposure_out,
+                       nullptr, stats ? stats : &local, t0));
+  RT_TRY(st.download(i_rgb, rgb8));
+  if (stats) stats->ms_total = rts::ms_since(t0);
+  return RT_OK;
 }
 
 }  // extern "C"

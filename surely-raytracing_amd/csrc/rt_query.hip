@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -13,8 +12,8 @@
 #include "rt_mi355x.h"
 #include "rt_query.h"
 #include "rt_flatten.hpp"
-#include "rt_scene_impl.hpp"
-#include "rt_variant.h"
+#include "rt_pass.hpp"
+#include "rt_stage.hpp"
 
 using namespace rtk;
 using namespace rts;
@@ -24,8 +23,7 @@ static_assert(sizeof(rt_ray) == 80 && sizeof(rt_hit) == 80 && sizeof(rt_query_pa
 
 namespace {
 
-// The AOV pass's five instances (rt_aov.hip): BVH (per-lane walker, the plan's 768-thread
-// workgroup), STAGED (table reads from the LDS copy), VN (nested volumes); every feature bit set.
+// The AOV pass's five instances (rt_aov.hip, RT_RETURN_INTERP_KERNEL); every feature bit set.
 // TraceParams stays the first argument, as in every kernel on this plan; the query's walker is
 // instantiated with PK and reads nothing through kparams() (rt_query.h). ANY: the five any-hit
 // instances, the same plan, workgroup and prologue.
@@ -40,11 +38,7 @@ typedef void (*query_kern_t)(TraceParams, const uint4*, void*, uint32_t, uint32_
                              uint32_t);
 template <bool ANY>
 query_kern_t query_kernel_of(const rtv::Variant& v) {
-  if (v.vn)
-    return v.bvh ? rt_query<true, false, RTL_VOLUME_NEST, ANY>
-                 : rt_query<false, false, RTL_VOLUME_NEST, ANY>;
-  if (v.staged) return rt_query<false, true, 0, ANY>;
-  return v.bvh ? rt_query<true, false, 0, ANY> : rt_query<false, false, 0, ANY>;
+  RT_RETURN_INTERP_KERNEL(v, rt_query, ANY);
 }
 query_kern_t query_kernel(const rtv::Variant& v, uint32_t mode) {
   return (mode & RT_QUERY_ANY_HIT) ? query_kernel_of<true>(v) : query_kernel_of<false>(v);
@@ -71,37 +65,34 @@ uint64_t out_bytes_of(const rt_query_params* qp, uint64_t n_rays) {
   return (qp->mode & RT_QUERY_OCCLUSION) ? n_rays : n_rays * sizeof(rt_hit);
 }
 
+// the scene's first query (sc->mu held, the device set): the prim table, n words then n prims
+int upload_prim_table(rt_scene* sc) {
+  std::vector<uint32_t> tab(sc->prim_word);
+  tab.insert(tab.end(), sc->prim_id.begin(), sc->prim_id.end());
+  tab.resize(tab.size() + 4, 0u);
+  uint32_t* d = nullptr;
+  HIP_TRY(hipMalloc(&d, tab.size() * 4));
+  const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return set_err(RT_ERR_HIP, std::string("upload prim table: ") + hipGetErrorString(e));
+  }
+  sc->prim_dev = d;
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int rt_query_rays_device(rt_scene* sc, const rt_query_params* qp, const rt_ray* rays,
                          uint64_t n_rays, void* out, void* stream_v, rt_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
+  const time_point t0 = std::chrono::steady_clock::now();
   RT_TRY(check_query_args(sc, qp, rays, n_rays, out));
   if (n_rays == 0) return RT_OK;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   std::unique_lock<std::mutex> lock(sc->mu);
   hipStream_t stream = (hipStream_t)stream_v;
-  HIP_TRY(hipSetDevice(sc->device));
-  const uint32_t n_prim = (uint32_t)sc->prim_word.size();
-  if (!sc->prim_dev) {  // the scene's first query: the prim table, n words then n prims
-    std::vector<uint32_t> tab(sc->prim_word);
-    tab.insert(tab.end(), sc->prim_id.begin(), sc->prim_id.end());
-    tab.resize(tab.size() + 4, 0u);
-    uint32_t* d = nullptr;
-    HIP_TRY(hipMalloc(&d, tab.size() * 4));
-    const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d);
-      return set_err(RT_ERR_HIP, std::string("upload prim table: ") + hipGetErrorString(e));
-    }
-    sc->prim_dev = d;
-  }
-  // a slot gives the query the scene's ordering and lifetime rules and the stats events
-  SlotHold hold{sc, lock};
-  RT_TRY(acquire_slot(sc, lock, stream, &hold.sl));
-  const LdsPlan LP = plan_lds(sc->hdr, sc->o_perl, qp->flags, false, sc->lds_module_max);
   // no camera: the kernel reads the tables, the plan's LDS regions, flags and seed
   rt_camera cam{};
   cam.image_width = cam.image_height = cam.sqrt_spp = cam.samples_per_pixel = 1;
@@ -109,24 +100,18 @@ int rt_query_rays_device(rt_scene* sc, const rt_query_params* qp, const rt_ray* 
   opts.seed = qp->seed;
   opts.flags = qp->flags;
   opts.row_step = 1;
-  TraceParams P;
-  fill_trace_params(&P, sc, &cam, &opts, LP);
-  P.sphere_light0 = -1;
-  const query_kern_t kern =
-      query_kernel(rtv::choose_variant(sc->hdr, qp->flags, LP.stage_scene != 0), qp->mode);
-  if (LP.lds_bytes > (64u << 10))
-    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)LP.lds_bytes));
-  int resident = 0;  // only asked: the grid is one lane per ray
-  RT_TRY(resident_blocks(sc, (const void*)kern, nullptr, LP.block, LP.lds_bytes, "query kernel",
-                         &resident));
-  hold.stream = stream;
-  hold.enqueued = true;  // from here on a failure still records `done` (SlotHold)
-  if (stats) HIP_TRY(hipEventRecord(hold.sl->ev0, stream));
+  SlotHold hold{sc, lock};
+  InterpPass ip;
+  RT_TRY(begin_interp_pass(sc, hold, stream, &cam, &opts, &ip));
+  const LdsPlan& LP = ip.LP;
+  if (!sc->prim_dev) RT_TRY(upload_prim_table(sc));
+  const query_kern_t kern = query_kernel(ip.v, qp->mode);
+  RT_TRY(arm_interp_launch(sc, hold, stream, (const void*)kern, LP, "query kernel",
+                           stats != nullptr));
   const unsigned blocks = (unsigned)((n_rays + (uint64_t)LP.block - 1) / (uint64_t)LP.block);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(LP.block), LP.lds_bytes, stream, P,
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(LP.block), LP.lds_bytes, stream, ip.P,
                      reinterpret_cast<const uint4*>(rays), out, (uint32_t)n_rays, qp->mode,
-                     (const uint32_t*)sc->prim_dev, n_prim);
+                     (const uint32_t*)sc->prim_dev, (uint32_t)sc->prim_word.size());
   HIP_TRY(hipGetLastError());
   rt_stats counts{};
   counts.samples = n_rays;
@@ -137,32 +122,20 @@ int rt_query_rays_device(rt_scene* sc, const rt_query_params* qp, const rt_ray* 
 
 int rt_query_rays(rt_scene* sc, const rt_query_params* qp, const rt_ray* rays, uint64_t n_rays,
                   void* out, rt_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
+  const time_point t0 = std::chrono::steady_clock::now();
   RT_TRY(check_query_args(sc, qp, rays, n_rays, out));
   if (n_rays == 0) return RT_OK;
-  const size_t in_bytes = (size_t)n_rays * sizeof(rt_ray), ob = (size_t)out_bytes_of(qp, n_rays);
-  HIP_TRY(hipSetDevice(sc->device));
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc(&d_in, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-  if (e == hipSuccess) e = hipMemcpy(d_in, rays, in_bytes, hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? RT_OK
-                           : set_err(RT_ERR_HIP, std::string("upload rays: ") + hipGetErrorString(e));
+  Staging st;
+  const int i_rays = st.add((size_t)n_rays * sizeof(rt_ray));
+  const int i_out = st.add((size_t)out_bytes_of(qp, n_rays));
+  RT_TRY(st.alloc(sc->device));
+  RT_TRY(st.upload(i_rays, rays));
   rt_stats local;
-  if (rc == RT_OK)
-    rc = rt_query_rays_device(sc, qp, (const rt_ray*)d_in, n_rays, d_out, nullptr,
-                              stats ? stats : &local);
-  if (rc == RT_OK) {
-    e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-      rc = set_err(RT_ERR_HIP, std::string("download hits: ") + hipGetErrorString(e));
-  }
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (rc == RT_OK && stats)
-    stats->ms_total =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  RT_TRY(rt_query_rays_device(sc, qp, st.ptr<const rt_ray>(i_rays), n_rays, st.ptr<void>(i_out),
+                              nullptr, stats ? stats : &local));
+  RT_TRY(st.download(i_out, out));
+  if (stats) stats->ms_total = ms_since(t0);
+  return RT_OK;
 }
 
 int rt_scene_prim_map(const rt_scene_blob* blob, uint32_t* node_word, uint32_t* prim, uint32_t cap,

@@ -1,8 +1,13 @@
 // rt_scene_impl.hpp — the host-side scene and render-slot types shared by the translation units of
 // librtmi355x.so that launch kernels on a scene, and the steps every such launch takes (argument
 // checks, LDS plan, TraceParams fill, occupancy query, completion): rt_device.hip (the path kernels
-// and the C ABI's scene functions, where everything declared here is defined) and rt_aov.hip (the
-// first-hit AOV pass). Internal: nothing here is part of the C ABI.
+// and the C ABI's scene functions, where everything declared here is defined), rt_tiles.hip and
+// rt_rays.hip (the tile-list and ray instances of the path kernels), rt_aov.hip (the first-hit AOV
+// pass) and rt_query.hip (the ray queries). The two passes on the interpreter's plan string these
+// steps together in rt_pass.hpp. The stage handles' translation units (rt_denoise.hip,
+// rt_temporal.hip, rt_adaptive.hip, rt_output.hip) know nothing of scenes and take only set_err,
+// HIP_TRY and RT_TRY from here, through rt_stage.hpp, which holds the handle lifecycle and the
+// host-buffer staging of every pass. Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

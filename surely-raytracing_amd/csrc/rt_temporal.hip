@@ -4,35 +4,27 @@
 // unit, built beside rt_denoise.hip; of scenes it knows nothing.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <string>
 
 #include "rt_mi355x.h"
 #include "rt_temporal.h"
-#include "rt_scene_impl.hpp"  // set_err, HIP_TRY
+#include "rt_stage.hpp"
 
 using namespace rtt;
 using rts::set_err;
+using rts::time_point;
 
-// One workspace and one ordering event per handle, as rt_denoiser. `mu` serialises the calls; a
-// call's stream waits for `done` of the call before it. The workspace holds two history sets of
-// 48 B per pixel; a call reads set `cur` and writes the other.
-struct rt_temporal {
-  int device = 0;
-  uint8_t* work = nullptr;
-  size_t work_bytes = 0;
+// The workspace holds two history sets of 48 B per pixel; a call reads set `cur` and writes the
+// other.
+struct rt_temporal : rts::Stage {
   int cur = 0;
   int hist_w = 0, hist_h = 0;  // 0 x 0: no history
   bool hist_m2 = false;
   uint64_t frames = 0;
   double center[3] = {0, 0, 0};  // of the camera that wrote the history
   double minv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the inverse of its M
-  hipEvent_t done = nullptr, ev0 = nullptr, ev1 = nullptr;
-  bool recorded = false;
-  std::mutex mu;
 };
 
 namespace {
@@ -118,26 +110,6 @@ int check_args(const rt_temporal* t, const rt_temporal_params* p, const rt_camer
   return RT_OK;
 }
 
-// Records `done` after whatever a failing call has enqueued, so that the next call still waits
-// for the kernel that may be using the workspace.
-struct DoneGuard {
-  rt_temporal* t;
-  hipStream_t stream;
-  bool finished = false;
-  ~DoneGuard() {
-    if (finished) return;
-    if (hipEventRecord(t->done, stream) == hipSuccess)
-      t->recorded = true;
-    else
-      (void)hipStreamSynchronize(stream);
-  }
-};
-
-typedef std::chrono::steady_clock::time_point time_point;
-double ms_since(time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the arguments checked, at least one pixel; inv: the inverse of cam's M
 int accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_camera* cam,
                       const double inv[9], const float* beauty, const float* m2, const float* aov,
@@ -154,17 +126,9 @@ int accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_came
                                           : "the history carries moments, but m2 is null");
   HIP_TRY(hipSetDevice(t->device));
   const size_t need = 2 * kSetBytesPerPixel * n_px;
-  if (need > t->work_bytes) {
-    // a frame of another size: the history is void, and the previous call may still be using it
-    if (t->recorded) HIP_TRY(hipEventSynchronize(t->done));
-    if (t->work) HIP_TRY(hipFree(t->work));
-    t->work = nullptr;
-    t->work_bytes = 0;
-    t->hist_w = t->hist_h = 0;
-    HIP_TRY(hipMalloc((void**)&t->work, need));
-    t->work_bytes = need;
-  }
-  if (t->recorded) HIP_TRY(hipStreamWaitEvent(stream, t->done, 0));
+  // a larger frame: the history is void, whether or not the new workspace can be had
+  if (need > t->work_bytes) t->hist_w = t->hist_h = 0;
+  RT_TRY(t->reserve(need));
   // the sets lie n_px * 48 B apart, for this frame size: a size change voids the history anyway
   const float4* hin = reinterpret_cast<const float4*>(t->work + (size_t)t->cur * kSetBytesPerPixel * n_px);
   float4* hout = reinterpret_cast<float4*>(t->work + (size_t)(1 - t->cur) * kSetBytesPerPixel * n_px);
@@ -190,8 +154,8 @@ int accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_came
   const unsigned tiles_y = ((unsigned)P.H + kTileH - 1) / kTileH;
   const dim3 grid(tiles_x * tiles_y), block(kBlock);  // W * H < 2^31: fewer than 2^28 + W + H tiles
   {
-    DoneGuard guard{t, stream};
-    if (stats) HIP_TRY(hipEventRecord(t->ev0, stream));
+    rts::Run run(*t, stream);
+    RT_TRY(run.begin(stats != nullptr));
     if (m2)
       hipLaunchKernelGGL(tp_accumulate<true>, grid, block, 0, stream, P, beauty, m2, aov, hin, hout,
                          out_beauty, out_m2, hist_len);
@@ -208,19 +172,10 @@ int accumulate_device(rt_temporal* t, const rt_temporal_params* p, const rt_came
     std::memcpy(t->center, cam->center, sizeof(t->center));
     std::memcpy(t->minv, inv, sizeof(t->minv));
     if (stats) HIP_TRY(hipEventRecord(t->ev1, stream));
-    HIP_TRY(hipEventRecord(t->done, stream));
-    t->recorded = true;
-    guard.finished = true;
   }
   if (stats) {
-    HIP_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-    stats->ms_kernel = ms;
-    stats->samples = n_px;
-    stats->out_bytes = (uint64_t)n_px * ((m2 ? 6 : 3) + (hist_len ? 1 : 0)) * sizeof(float);
-    stats->launches = 1u;
-    stats->ms_total = ms_since(t0);
+    const uint64_t out_bytes = (uint64_t)n_px * ((m2 ? 6 : 3) + (hist_len ? 1 : 0)) * sizeof(float);
+    RT_TRY(t->finish_stats(stream, stats, n_px, out_bytes, 1u, t0));
   }
   return RT_OK;
 }
@@ -246,39 +201,10 @@ int rt_temporal_default_params(int width, int height, rt_temporal_params* out) {
 }
 
 int rt_temporal_create(int device, rt_temporal** out) {
-  if (!out) return set_err(RT_ERR_INVALID_ARG, "null out");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_err(RT_ERR_NO_DEVICE, "no HIP device available");
-  if (device < 0 || device >= ndev) return set_err(RT_ERR_INVALID_ARG, "bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-  rt_temporal* t = new rt_temporal;
-  t->device = device;
-  hipError_t e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&t->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&t->ev1);
-  if (e != hipSuccess) {
-    rt_temporal_destroy(t);
-    return set_err(RT_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = t;
-  return RT_OK;
+  return rts::stage_create(device, true, out);
 }
 
-void rt_temporal_destroy(rt_temporal* t) {
-  if (!t) return;
-  {
-    std::lock_guard<std::mutex> lock(t->mu);
-    (void)hipSetDevice(t->device);
-    if (t->recorded) (void)hipEventSynchronize(t->done);
-    if (t->work) (void)hipFree(t->work);
-    if (t->done) (void)hipEventDestroy(t->done);
-    if (t->ev0) (void)hipEventDestroy(t->ev0);
-    if (t->ev1) (void)hipEventDestroy(t->ev1);
-  }
-  delete t;
-}
+void rt_temporal_destroy(rt_temporal* t) { rts::stage_destroy(t); }
 
 int rt_temporal_info(rt_temporal* t, uint64_t* out, int n) {
   if (!t || !out || n < 0) return set_err(RT_ERR_INVALID_ARG, "null argument");
@@ -309,40 +235,29 @@ int rt_temporal_accumulate(rt_temporal* t, const rt_temporal_params* p, const rt
                            float* out_beauty, float* out_m2, float* hist_len, rt_stats* stats) {
   const time_point t0 = std::chrono::steady_clock::now();
   double inv[9];
-  int rc = check_args(t, p, cam, beauty, m2, aov, out_beauty, out_m2, inv);
+  const int rc = check_args(t, p, cam, beauty, m2, aov, out_beauty, out_m2, inv);
   if (rc != RT_OK) return rc;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (p->height == 0) return RT_OK;
   const size_t n_px = (size_t)p->width * (size_t)p->height;
   const size_t b_bytes = n_px * 3 * sizeof(float), a_bytes = n_px * RT_AOV_CHANNELS * sizeof(float);
-  const size_t m_bytes = m2 ? b_bytes : 0, l_bytes = hist_len ? n_px * sizeof(float) : 0;
-  HIP_TRY(hipSetDevice(t->device));
-  // one allocation: the beauty frame and the moments (both accumulated in place), the AOVs, the
-  // history lengths
-  uint8_t* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, b_bytes + m_bytes + a_bytes + l_bytes));
-  float* const d_beauty = reinterpret_cast<float*>(d);
-  float* const d_m2 = m2 ? reinterpret_cast<float*>(d + b_bytes) : nullptr;
-  float* const d_aov = reinterpret_cast<float*>(d + b_bytes + m_bytes);
-  float* const d_len =
-      hist_len ? reinterpret_cast<float*>(d + b_bytes + m_bytes + a_bytes) : nullptr;
-  hipError_t e = hipMemcpy(d_beauty, beauty, b_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess && m2) e = hipMemcpy(d_m2, m2, m_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_aov, aov, a_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+  // the beauty frame and the moments (both accumulated in place), the AOVs, the history lengths
+  rts::Staging st;
+  const int i_beauty = st.add(b_bytes), i_m2 = st.add_if(m2 != nullptr, b_bytes);
+  const int i_aov = st.add(a_bytes), i_len = st.add_if(hist_len != nullptr, n_px * sizeof(float));
+  RT_TRY(st.alloc(t->device));
+  RT_TRY(st.upload(i_beauty, beauty));
+  RT_TRY(st.upload(i_m2, m2));
+  RT_TRY(st.upload(i_aov, aov));
+  float *const d_beauty = st.ptr<float>(i_beauty), *const d_m2 = st.ptr<float>(i_m2);
   rt_stats local;
-  if (rc == RT_OK)
-    rc = accumulate_device(t, p, cam, inv, d_beauty, d_m2, d_aov, d_beauty, d_m2, d_len, nullptr,
-                           stats ? stats : &local, t0);
-  if (rc == RT_OK) {
-    e = hipMemcpy(out_beauty, d_beauty, b_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && m2) e = hipMemcpy(out_m2, d_m2, m_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && hist_len) e = hipMemcpy(hist_len, d_len, l_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RT_ERR_HIP, std::string("download: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(d);
-  if (rc == RT_OK && stats) stats->ms_total = ms_since(t0);
-  return rc;
+  RT_TRY(accumulate_device(t, p, cam, inv, d_beauty, d_m2, st.ptr<float>(i_aov), d_beauty, d_m2,
+                           st.ptr<float>(i_len), nullptr, stats ? stats : &local, t0));
+  RT_TRY(st.download(i_beauty, out_beauty));
+  RT_TRY(st.download(i_m2, out_m2));
+  RT_TRY(st.download(i_len, hist_len));
+  if (stats) stats->ms_total = rts::ms_since(t0);
+  return RT_OK;
 }
 
 }  // extern "C"

@@ -35,6 +35,25 @@ def test_abi_version_and_error_string():
     assert isinstance(lib.rt_last_error(), bytes)
 
 
+@pytest.mark.parametrize("stage", ["denoiser", "temporal", "adaptive", "output"])
+def test_stage_create_checks(stage):
+    """The four stage handles are created by one function (csrc/rt_stage.hpp): a null out pointer
+    is refused first; then *out is null whenever the call fails, with RT_ERR_NO_DEVICE where no
+    device is visible and RT_ERR_INVALID_ARG for an ordinal no device has."""
+    lib = rt.device_lib()
+    create = getattr(lib, f"rt_{stage}_create")
+    assert create(0, None) == rt.RT_ERR_INVALID_ARG
+    assert b"null out" in lib.rt_last_error()
+    h = C.c_void_p(0x1000)  # must be overwritten
+    if rt.device_count() <= 0:
+        assert create(0, C.byref(h)) == rt.RT_ERR_NO_DEVICE
+        assert b"no HIP device available" in lib.rt_last_error()
+    else:
+        assert create(10 ** 6, C.byref(h)) == rt.RT_ERR_INVALID_ARG
+        assert b"bad device ordinal" in lib.rt_last_error()
+    assert h.value is None
+
+
 def test_validate_accepts_all_presets():
     lib = rt.device_lib()
     for name in ["cornell_box", "cornell_smoke", "final_scene", "quads", "simple_light",

@@ -15,7 +15,7 @@ import pytest
 
 import surely_rt as rt
 from adaptive_cases import Case, bits, sentinel
-from hip_buf import DevBuf
+from hip_buf import DevBuf, Stream
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +149,46 @@ def test_resolve_against_numpy(ad):
         b.free()
         o.free()
         sm.free()
+
+
+def test_two_streams_through_one_handle_bitwise(gpu_available):
+    """One handle's workspace and host copy of rows_held serve calls on two streams, small frame,
+    large frame, small frame, ...: each call must wait for the one before it, through a workspace
+    growth too. Bitwise against a fresh handle's serial results."""
+    g = np.random.default_rng(5)
+    sizes = [(20, 12), (72, 40)]  # 6 and 45 tiles
+    rows = [g.integers(1, S + 1, int(np.prod(rt.tile_grid(w, h)))).astype(np.uint32)
+            for w, h in sizes]
+    assert [r.size for r in rows] == [6, 45]
+    assert all(len(set(r.tolist())) > 1 for r in rows) and set(rows[1].tolist()) == {1, 2, 3, 4}
+    accs = [g.uniform(0.0, 50.0, (h, w, 3)).astype(np.float32) for w, h in sizes]
+    bufs = [(DevBuf(a.shape, init=a), DevBuf(a.shape), DevBuf(a.shape[:2])) for a in accs]
+    streams = [Stream(0), Stream(0)]
+    fresh, one = rt.Adaptive(), rt.Adaptive()
+    try:
+        serial = []
+        for (w, h), r, (b, o, sm) in zip(sizes, rows, bufs):
+            fresh.resolve_device(w, h, S, r, b.ptr, o.ptr, sm.ptr)
+            serial.append((o.download(), sm.download()))
+            o.upload(sentinel(o.shape))
+            sm.upload(sentinel(sm.shape))
+        assert all(np.isfinite(out).all() and (smp > 0).all() for out, smp in serial)
+        for _ in range(3):
+            for (w, h), r, (b, o, sm), s in zip(sizes, rows, bufs, streams):
+                one.resolve_device(w, h, S, r, b.ptr, o.ptr, sm.ptr, stream=s.handle)
+        for s in streams:
+            s.sync()
+        for (b, o, sm), (out, smp) in zip(bufs, serial):
+            assert np.array_equal(bits(o.download()), bits(out))
+            assert np.array_equal(bits(sm.download()), bits(smp))
+    finally:
+        for s in streams:
+            s.destroy()
+        for t in bufs:
+            for d in t:
+                d.free()
+        fresh.close()
+        one.close()
 
 
 def params(P, min_passes, threshold):
