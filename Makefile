@@ -11,6 +11,7 @@ PKG      := surely-raytracing_amd
 CSRC     := $(PKG)/csrc
 BUILD    := build
 HIPCC    ?= /opt/rocm/bin/hipcc
+ROCM     ?= $(abspath $(dir $(HIPCC))..)
 ARCH     ?= gfx950
 # device path is f64; contraction off, fma written explicitly (deterministic bits)
 HIPFLAGS := --offload-arch=$(ARCH) -Iinclude -I$(BUILD) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
@@ -18,7 +19,7 @@ CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra
 CFLAGS_O := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function
 
 HOST_SRC := $(CSRC)/host/scene.cpp $(CSRC)/host/presets.cpp $(CSRC)/host/capi.cpp
-DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_rays.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
+DEV_SRC  := $(CSRC)/rt_device.hip $(CSRC)/rt_tiles.hip $(CSRC)/rt_rays.hip $(CSRC)/rt_aov.hip $(CSRC)/rt_query.hip $(CSRC)/rt_denoise.hip $(CSRC)/rt_temporal.hip $(CSRC)/rt_adaptive.hip $(CSRC)/rt_output.hip $(CSRC)/rt_raygen.hip $(CSRC)/rt_flatten.cpp $(CSRC)/rt_obvh.cpp $(CSRC)/rt_jit.cpp
 DEV_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_rng.h $(CSRC)/rt_layout.h $(CSRC)/rt_flatten.hpp $(CSRC)/rt_jit.hpp $(CSRC)/rt_scene_impl.hpp $(CSRC)/rt_stage.hpp $(CSRC)/rt_pass.hpp $(CSRC)/rt_variant.h include/rt_mi355x.h $(BUILD)/rt_jit_sources.inc
 JIT_HDR  := $(CSRC)/rt_kernel.h $(CSRC)/rt_layout.h include/rt_mi355x.h $(CSRC)/rt_rng.h
 
@@ -41,7 +42,7 @@ $(BUILD)/rt_jit_sources.inc: $(JIT_HDR) $(CSRC)/embed_sources.py
 # one object per source, so an edit of the host-side generator or flattener does not recompile
 # the kernels (rt_device.hip: every ahead-of-time template instance, ~3 minutes)
 OBJ      := $(BUILD)/obj
-DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_rays.o $(OBJ)/rt_aov.o $(OBJ)/rt_query.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
+DEV_OBJ  := $(OBJ)/rt_device.o $(OBJ)/rt_tiles.o $(OBJ)/rt_rays.o $(OBJ)/rt_aov.o $(OBJ)/rt_query.o $(OBJ)/rt_denoise.o $(OBJ)/rt_temporal.o $(OBJ)/rt_adaptive.o $(OBJ)/rt_output.o $(OBJ)/rt_raygen.o $(OBJ)/rt_flatten.o $(OBJ)/rt_obvh.o $(OBJ)/rt_jit.o
 $(OBJ)/rt_device.o: $(CSRC)/rt_device.hip $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -61,6 +62,10 @@ $(OBJ)/rt_adaptive.o: $(CSRC)/rt_adaptive.hip $(DEV_HDR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the output stage: auto-exposure reduction, exposure / gamma / RGB8 conversion, the handle
 $(OBJ)/rt_output.o: $(CSRC)/rt_output.hip $(DEV_HDR)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# the ray generators: projection and AO ray kernels, the AO count, the handle and the AO driver
+$(OBJ)/rt_raygen.o: $(CSRC)/rt_raygen.hip $(CSRC)/rt_frame3.h $(DEV_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the first-hit AOV kernels (rt_aov.h is ahead-of-time only: not one of JIT_HDR)
@@ -91,12 +96,12 @@ $(BUILD)/librtgather.so: $(CSRC)/rt_gather.hip include/rt_gather.h include/rt_mi
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -shared $(CSRC)/rt_gather.hip -o $@ -lrccl
 
-$(BUILD)/librthost.so: $(HOST_SRC) $(CSRC)/host/scene.hpp include/rt_host.h include/rt_mi355x.h
+$(BUILD)/librthost.so: $(HOST_SRC) $(CSRC)/host/scene.hpp $(CSRC)/rt_frame3.h include/rt_host.h include/rt_mi355x.h
 	@mkdir -p $(BUILD)
 	g++ $(CXXFLAGS) -shared $(HOST_SRC) -o $@
 
 $(BUILD)/rt_render_cli: $(CSRC)/host/rt_render_cli.cpp $(BUILD)/librthost.so $(BUILD)/librtmi355x.so
-	g++ $(CXXFLAGS) $< -o $@ -L$(BUILD) -lrthost -lrtmi355x -Wl,-rpath,'$$ORIGIN'
+	g++ $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -isystem $(ROCM)/include $< -o $@ -L$(BUILD) -lrthost -lrtmi355x -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(ROCM)/lib
 
 # host check of the split stream key against rng_seed (tests/test_rng_key.py runs it)
 $(BUILD)/rng_key_check: $(CSRC)/host/rng_key_check.cpp $(CSRC)/rt_rng.h

@@ -967,6 +967,113 @@ int rt_render_rays_device(rt_scene* scene, const rt_rays_params* params, const r
 int rt_render_rays(rt_scene* scene, const rt_rays_params* params, const rt_ray* rays,
                    uint64_t n_rays, float* rgb, rt_stats* stats);
 
+/* ---- ray generators on the device: projection rays, AO ray batches, an AO frame -------------------
+ * rt_query_rays and rt_render_rays answer rays at device speed; these entry points form the rays
+ * there too, so a panorama, fisheye or ortho frame and an ambient-occlusion frame need no host loop
+ * and no transfer of 80-byte records. The host generators of rt_host.h (rth_projection_rays,
+ * rth_ao_rays) remain the definition of every field; the kernels restate them in f64 with the
+ * host's operations in the host's order, fma exactly where the host writes fma. Pinhole and ortho
+ * rays, and every field of the other kinds that takes no sin, cos, atan2 or hypot, are therefore
+ * the host's bit for bit; a panorama, fisheye or AO direction differs from the host's by the last
+ * bits of those four functions (the device math library's against the host libm's; DESIGN.md
+ * section 4.2k gives the measured bound).
+ *
+ * rt_raygen is a stage handle as rt_output_stage: a device ordinal, a workspace (used by
+ * rt_ambient_occlusion_device alone) and an ordering event. Calls on one handle are serialised
+ * and ordered, whatever streams they go to. Every call is asynchronous on hip_stream (may be
+ * NULL); stats != NULL synchronises.
+ *
+ * rt_projection_rays_device: rth_projection_rays restricted to the frame rows [row_begin,
+ * row_begin + n_rows) of ONE stratum (s_i, s_j). With W the frame width, ray (i, j) goes to
+ * rays_dev[(j - row_begin) * W + i] and carries pixel = j * W + i, so a frame can be generated and
+ * consumed in bands. proj has the layout and the meaning of rth_projection, RT_PROJ_* the values of
+ * RTH_PROJ_*; cam is read for RT_PROJ_PINHOLE only (its width, height and sqrt_spp are then the
+ * frame's). The frame vectors f, r, u are formed on the host by rth_projection_rays' own code and
+ * reach the kernel as arguments. Checked as rth_projection_rays checks (sizes >= 1 and width *
+ * height < 2^31, a stratum outside sqrt_spp, an unknown kind, a zero or non-finite frame vector, a
+ * non-finite origin, a non-positive fov where it is read), and: row_begin < 0, n_rows < 0,
+ * row_begin + n_rows > height, rays_dev not 16-byte aligned. n_rows == 0 returns RT_OK and touches
+ * nothing. rt_stats: samples = rays written, out_bytes = 80 per ray, launches = 1.
+ *
+ * rt_ao_rays_device: rth_ao_rays on device buffers: from n primary rays and their records
+ * (rt_query_rays_device, record mode) the dir_index-th cosine-distributed direction about each
+ * hit's normal, origin = hits[i].p, time and pixel the primary's, sample = dir_index, the interval
+ * [tmin, radius]. A lane whose hits[i].hit != 1 writes an all-zero origin and dir (an invalid ray:
+ * the query answers 255). out_dev may be primary_dev. rt_stats as above.
+ *
+ * rt_ao_accumulate_device: for every ray i and c < channels
+ *   sums[i * channels + c] = (flags & RT_FLAG_OVERWRITE ? 0 : old) + (occ[i] == 0 ? 1.0f : 0.0f),
+ * so the bytes 1 (occluded) and 255 (no surface: an invalid AO ray) add nothing and a pixel that
+ * saw no surface stays black. channels is 1 or 3 (the count replicated: what rt_output and
+ * rt_denoise take). rt_stats: samples = n, out_bytes = 4 * channels per ray, launches = 1.
+ *
+ * rt_ambient_occlusion_device: the ambient-occlusion frame of n primary rays without a host round
+ * trip. Per chunk of at most chunk_rays rays: a record-mode rt_query_rays_device of the primaries
+ * into the workspace (into hits_out_dev if given), then for k = 0 .. directions-1
+ * rt_ao_rays_device with dir_index = k into the workspace, an any-hit query (RT_QUERY_OCCLUSION |
+ * RT_QUERY_ANY_HIT, the caller's RT_FLAG_REFERENCE_BVH, the params' seed) into workspace bytes and
+ * rt_ao_accumulate_device, which overwrites at k == 0 only, and only when RT_FLAG_OVERWRITE is set.
+ * sums_dev[i * channels + c] ends as the number of unoccluded directions of ray i (plus its old
+ * value without RT_FLAG_OVERWRITE): divide by `directions`, or hand it to rt_output with
+ * samples_per_pixel = directions. Everything goes on hip_stream; nothing waits on the host unless
+ * stats != NULL. A ray's result depends on that ray and the params alone, so the chunking is
+ * invisible in the output; the workspace is at most 161 bytes x the chunk. The scene must live on
+ * the handle's device. rt_stats: samples = n * directions; launches = the kernel launches of the
+ * call; ms_kernel = the sum over those launches; out_bytes = the bytes written to the caller's
+ * buffers (sums, and hits_out_dev if given).
+ *
+ * Checked before the handle is read and before any HIP call, RT_ERR_INVALID_ARG each: null
+ * pointers (hits_out_dev and stats may be NULL); n >= 2^31; ray or hit buffers not 16-byte
+ * aligned; _pad0 != 0; a tmin that is not finite or < 0; a radius that is NaN or <= tmin;
+ * directions == 0; channels not 1 or 3; unknown flag bits (rt_ao_accumulate_device takes
+ * RT_FLAG_OVERWRITE, rt_ambient_occlusion_device RT_FLAG_OVERWRITE | RT_FLAG_REFERENCE_BVH); and
+ * the projection's checks above. n == 0 returns RT_OK and touches nothing.
+ *
+ * Not covered: sorting or compacting rays, bent normals, distance-weighted AO, rt_multi_*. */
+#define RT_PROJ_PINHOLE 0   /* values and meaning of RTH_PROJ_* (rt_host.h) */
+#define RT_PROJ_ORTHO 1
+#define RT_PROJ_PANORAMA 2
+#define RT_PROJ_FISHEYE 3
+typedef struct rt_projection {   /* 96 bytes, the layout of rth_projection */
+  int32_t kind;
+  int32_t width, height, sqrt_spp;
+  double origin[3], forward[3], up[3];
+  double fov;
+} rt_projection;
+typedef struct rt_ao_params {    /* 32 bytes, the layout of rth_ao_params */
+  uint64_t seed;
+  double radius;
+  double tmin;
+  uint32_t dir_index;
+  uint32_t _pad0;
+} rt_ao_params;
+typedef struct rt_ao_frame_params {  /* 40 bytes, no padding */
+  uint64_t seed;
+  double radius;
+  double tmin;
+  uint32_t directions;   /* K >= 1 */
+  uint32_t flags;        /* RT_FLAG_OVERWRITE | RT_FLAG_REFERENCE_BVH only */
+  uint32_t channels;     /* 1 or 3 (the count replicated: what rt_output / rt_denoise take) */
+  uint32_t chunk_rays;   /* 0 = default (2^22); else rays per internal chunk, >= 1 */
+} rt_ao_frame_params;
+
+typedef struct rt_raygen rt_raygen;  /* opaque: device ordinal, workspace, ordering event */
+int  rt_raygen_create(int device, rt_raygen** out);
+void rt_raygen_destroy(rt_raygen* g);
+
+int rt_projection_rays_device(rt_raygen* g, const rt_projection* proj, const rt_camera* cam,
+                              uint64_t seed, int32_t s_i, int32_t s_j, int32_t row_begin,
+                              int32_t n_rows, rt_ray* rays_dev, void* hip_stream, rt_stats* stats);
+int rt_ao_rays_device(rt_raygen* g, const rt_ao_params* p, const rt_ray* primary_dev,
+                      const rt_hit* hits_dev, uint64_t n, rt_ray* out_dev, void* hip_stream,
+                      rt_stats* stats);
+int rt_ao_accumulate_device(rt_raygen* g, const uint8_t* occ_dev, uint64_t n, uint32_t channels,
+                            uint32_t flags, float* sums_dev, void* hip_stream, rt_stats* stats);
+int rt_ambient_occlusion_device(rt_raygen* g, rt_scene* scene, const rt_ao_frame_params* p,
+                                const rt_ray* primary_dev, uint64_t n, float* sums_dev,
+                                rt_hit* hits_out_dev /* may be NULL */, void* hip_stream,
+                                rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,12 @@ pub const RT_QUERY_ANY_HIT: u32 = 0x2; // with RT_QUERY_OCCLUSION only
 pub const RT_RAYS_STREAM_TIME: u32 = 0x1;
 pub const RT_RAYS_MAX_SKIP: u32 = 16;
 
+// ray generators on the device (rt_projection.kind)
+pub const RT_PROJ_PINHOLE: i32 = 0;
+pub const RT_PROJ_ORTHO: i32 = 1;
+pub const RT_PROJ_PANORAMA: i32 = 2;
+pub const RT_PROJ_FISHEYE: i32 = 3;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct rt_scene_blob {
@@ -270,7 +276,46 @@ pub struct rt_rays_params {
     pub background: [f64; 3],
 }
 
-/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage, rt_temporal).
+/// A projection of rt_projection_rays_device; 96 bytes, the layout of rth_projection.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_projection {
+    pub kind: i32, // RT_PROJ_*
+    pub width: i32,
+    pub height: i32,
+    pub sqrt_spp: i32,
+    pub origin: [f64; 3],
+    pub forward: [f64; 3],
+    pub up: [f64; 3],
+    pub fov: f64,
+}
+
+/// Parameters of rt_ao_rays_device; 32 bytes, the layout of rth_ao_params.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_ao_params {
+    pub seed: u64,
+    pub radius: f64,    // becomes tmax; > tmin, may be +inf
+    pub tmin: f64,      // finite, >= 0
+    pub dir_index: u32, // k: which of the K directions this batch is
+    pub _pad0: u32,     // must be 0
+}
+
+/// Parameters of rt_ambient_occlusion_device; 40 bytes, no padding.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct rt_ao_frame_params {
+    pub seed: u64,
+    pub radius: f64,
+    pub tmin: f64,
+    pub directions: u32, // K >= 1
+    pub flags: u32,      // RT_FLAG_OVERWRITE | RT_FLAG_REFERENCE_BVH only
+    pub channels: u32,   // 1 or 3
+    pub chunk_rays: u32, // 0 = default (2^22); else rays per internal chunk
+}
+
+/// Opaque handles (rt_scene, rt_multi, rt_denoiser, rt_adaptive, rt_output_stage, rt_temporal,
+/// rt_raygen).
 #[repr(C)]
 pub struct rt_scene {
     _private: [u8; 0],
@@ -293,6 +338,10 @@ pub struct rt_output_stage {
 }
 #[repr(C)]
 pub struct rt_temporal {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct rt_raygen {
     _private: [u8; 0],
 }
 
@@ -432,4 +481,21 @@ extern "C" {
     pub fn rt_render_rays(scene: *mut rt_scene, params: *const rt_rays_params,
                           rays: *const rt_ray, n_rays: u64, rgb: *mut f32,
                           stats: *mut rt_stats) -> c_int;
+    pub fn rt_raygen_create(device: c_int, out: *mut *mut rt_raygen) -> c_int;
+    pub fn rt_raygen_destroy(g: *mut rt_raygen);
+    pub fn rt_projection_rays_device(g: *mut rt_raygen, proj: *const rt_projection,
+                                     cam: *const rt_camera, seed: u64, s_i: i32, s_j: i32,
+                                     row_begin: i32, n_rows: i32, rays_dev: *mut rt_ray,
+                                     hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_ao_rays_device(g: *mut rt_raygen, p: *const rt_ao_params,
+                             primary_dev: *const rt_ray, hits_dev: *const rt_hit, n: u64,
+                             out_dev: *mut rt_ray, hip_stream: *mut c_void,
+                             stats: *mut rt_stats) -> c_int;
+    pub fn rt_ao_accumulate_device(g: *mut rt_raygen, occ_dev: *const u8, n: u64, channels: u32,
+                                   flags: u32, sums_dev: *mut f32, hip_stream: *mut c_void,
+                                   stats: *mut rt_stats) -> c_int;
+    pub fn rt_ambient_occlusion_device(g: *mut rt_raygen, scene: *mut rt_scene,
+                                       p: *const rt_ao_frame_params, primary_dev: *const rt_ray,
+                                       n: u64, sums_dev: *mut f32, hits_out_dev: *mut rt_hit,
+                                       hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
 }

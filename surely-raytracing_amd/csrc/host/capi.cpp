@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../../include/rt_host.h"
+#include "../rt_frame3.h"
 #include "scene.hpp"
 
 using namespace rt;
@@ -267,17 +268,9 @@ double host_rnd(HostRng& g) {
   g.s1 = rotl32(s1, 13);
   return (double)result * 0x1p-32;
 }
-bool unit3(const double* v, double* out) {
-  const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  if (!(n > 0.0) || !std::isfinite(n)) return false;
-  for (int k = 0; k < 3; ++k) out[k] = v[k] / n;
-  return true;
-}
-void cross3(const double* a, const double* b, double* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
+// the view frame's helpers: shared with the device generator's host side (rt_raygen.hip)
+using rtframe::cross3;
+using rtframe::unit3;
 }  // namespace
 
 int rth_projection_rays(const rth_projection* pr, const rt_camera* cam, uint64_t seed, int32_t s_i,

@@ -26,6 +26,11 @@
 //      go to one record query, then K passes of rth_ao_rays and an any-hit query (RT_QUERY_ANY_HIT)
 //      over [1e-4, R] (default: no limit); a pixel is unoccluded / K in all three channels through
 //      write_color, a pixel that sees no surface 0; does not combine with the render modes
+//   -> with --device-rays: the rays of --ao and --projection are formed on the GPU and stay there.
+//      --ao: the primaries are uploaded once, rt_ambient_occlusion_device counts the unoccluded
+//      directions and rt_output_device writes the frame; --projection: each pass's rays come from
+//      rt_projection_rays_device straight into the buffer rt_render_rays_device reads, the sums
+//      are downloaded once. Without the flag both run as above.
 //
 // Usage: rt_render_cli [--scene N|name] [--variant mixed_pdf] [--width W] [--spp S]
 //                      [--depth D] [--aspect A] [--seed K] [--build-seed K] [--device N]
@@ -33,7 +38,7 @@
 //                      [--denoise-var [levels]] [--adaptive threshold] [--passes P] [--floor F]
 //                      [--device-output] [--frames N] [--orbit DEG] [--temporal] [--out file.ppm]
 //                      [--pick X Y] [--projection ortho|panorama|fisheye] [--fov F]
-//                      [--ao K] [--ao-radius R]
+//                      [--ao K] [--ao-radius R] [--device-rays]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -42,6 +47,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>  // --device-rays: the buffers the *_device calls take
 
 #include "../../../include/rt_host.h"
 #include "../../../include/rt_mi355x.h"
@@ -217,16 +224,21 @@ static int pick_pixel(const rt_scene_blob& blob, const rt_camera& cam, int x, in
   return 0;
 }
 
-// --ao K: ambient occlusion of the first hits. Record query, K x (rth_ao_rays, any-hit query).
-static int render_ao(const rt_scene_blob& blob, const rt_camera& cam, int K, double radius,
-                     uint64_t seed, int device, const std::string& out) {
+// --device-rays: one device allocation, freed on every exit path
+struct DeviceBuffer {
+  void* p = nullptr;
+  ~DeviceBuffer() {
+    if (p) (void)hipFree(p);
+  }
+  bool alloc(int device, size_t bytes) {
+    return hipSetDevice(device) == hipSuccess && hipMalloc(&p, bytes) == hipSuccess;
+  }
+};
+
+// the pixel-centre rays of --ao, each formed as --pick forms its one ray
+static std::vector<rt_ray> pixel_centre_rays(const rt_camera& cam) {
   const int W = cam.image_width, H = cam.image_height;
-  const size_t n = (size_t)W * H;
-  // std::vector's allocation is 16-byte aligned for these 80-byte records (operator new)
-  std::vector<rt_ray> primary(n), ao(n);
-  std::vector<rt_hit> hits(n);
-  std::vector<uint8_t> occ(n);
-  std::vector<float> sums(3 * n, 0.0f);
+  std::vector<rt_ray> primary((size_t)W * H);  // operator new: 16-byte aligned
   for (int y = 0; y < H; ++y)
     for (int x = 0; x < W; ++x) {
       rt_ray& r = primary[(size_t)y * W + x];
@@ -240,6 +252,20 @@ static int render_ao(const rt_scene_blob& blob, const rt_camera& cam, int K, dou
       r.tmax = HUGE_VAL;
       r.pixel = (uint32_t)(y * W + x);
     }
+  return primary;
+}
+
+// --ao K: ambient occlusion of the first hits. Record query, K x (rth_ao_rays, any-hit query).
+static int render_ao(const rt_scene_blob& blob, const rt_camera& cam, int K, double radius,
+                     uint64_t seed, int device, const std::string& out) {
+  const int W = cam.image_width, H = cam.image_height;
+  const size_t n = (size_t)W * H;
+  // std::vector's allocation is 16-byte aligned for these 80-byte records (operator new)
+  const std::vector<rt_ray> primary = pixel_centre_rays(cam);
+  std::vector<rt_ray> ao(n);
+  std::vector<rt_hit> hits(n);
+  std::vector<uint8_t> occ(n);
+  std::vector<float> sums(3 * n, 0.0f);
   rt_query_params qp;
   std::memset(&qp, 0, sizeof(qp));
   qp.seed = seed;
@@ -283,12 +309,77 @@ static int render_ao(const rt_scene_blob& blob, const rt_camera& cam, int K, dou
   return 0;
 }
 
+// --ao K --device-rays: the primaries go up once; records, AO rays, occlusion bytes and the count
+// stay on the device (rt_ambient_occlusion_device), rt_output_device writes the RGB8 frame.
+static int render_ao_device(const rt_scene_blob& blob, const rt_camera& cam, int K, double radius,
+                            uint64_t seed, int device, const std::string& out) {
+  const int W = cam.image_width, H = cam.image_height;
+  const size_t n = (size_t)W * H;
+  const std::vector<rt_ray> primary = pixel_centre_rays(cam);
+  DeviceBuffer d_primary, d_sums, d_rgb;
+  if (!d_primary.alloc(device, n * sizeof(rt_ray)) || !d_sums.alloc(device, 3 * n * sizeof(float)) ||
+      !d_rgb.alloc(device, 3 * n) ||
+      hipMemcpy(d_primary.p, primary.data(), n * sizeof(rt_ray), hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    std::fprintf(stderr, "--device-rays: device buffers: %s\n",
+                 hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  rt_ao_frame_params fp;
+  std::memset(&fp, 0, sizeof(fp));
+  fp.seed = seed;
+  fp.radius = radius;
+  fp.tmin = 1e-4;
+  fp.directions = (uint32_t)K;
+  fp.flags = RT_FLAG_OVERWRITE;
+  fp.channels = 3;
+  rt_output_params op;
+  std::memset(&op, 0, sizeof(op));
+  op.width = W;
+  op.height = H;
+  op.samples_per_pixel = (double)K;
+  rt_scene* sc = nullptr;
+  rt_raygen* rg = nullptr;
+  rt_output_stage* os = nullptr;
+  rt_stats st, st_out;
+  std::vector<uint8_t> rgb(3 * n);
+  int rc = rt_scene_create(&blob, device, &sc);
+  if (rc == RT_OK) rc = rt_raygen_create(device, &rg);
+  if (rc == RT_OK) rc = rt_output_create(device, &os);
+  if (rc == RT_OK)
+    rc = rt_ambient_occlusion_device(rg, sc, &fp, (const rt_ray*)d_primary.p, n, (float*)d_sums.p,
+                                     nullptr, nullptr, &st);
+  if (rc == RT_OK)
+    rc = rt_output_device(os, &op, (const float*)d_sums.p, (uint8_t*)d_rgb.p, nullptr, nullptr,
+                          &st_out);
+  if (rc != RT_OK) std::fprintf(stderr, "--ao --device-rays: %d %s\n", rc, rt_last_error());
+  rt_output_destroy(os);
+  rt_raygen_destroy(rg);
+  rt_scene_destroy(sc);
+  if (rc != RT_OK) return 1;
+  if (hipMemcpy(rgb.data(), d_rgb.p, 3 * n, hipMemcpyDeviceToHost) != hipSuccess) {
+    std::fprintf(stderr, "--device-rays: download: %s\n", hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  if (rth_write_ppm(out.c_str(), rgb.data(), W, H) != 0) {
+    std::fprintf(stderr, "%s\n", rth_last_error());
+    return 1;
+  }
+  std::fprintf(stderr,
+               "ambient occlusion %dx%d, %d directions, radius %g, rays on the device: %.3f ms in %u "
+               "kernels, output %.3f ms -> %s\n",
+               W, H, K, radius, st.ms_kernel, st.launches, st_out.ms_kernel, out.c_str());
+  return 0;
+}
+
 // --projection: the preset's eye and view frame, another projection. fov <= 0: the height of the
 // pinhole's viewport for ortho, 180 degrees for fisheye. Pixels whose ray is invalid (a fisheye
 // pixel outside the sphere) come back NaN and are written black.
+// device_rays: each pass's rays are formed by rt_projection_rays_device in the buffer
+// rt_render_rays_device reads; the sums stay on the device until the last pass.
 static int render_projection(const rt_scene_blob& blob, const rt_camera& cam, int kind, double fov,
-                             uint64_t seed, uint32_t flags, int device, std::vector<float>& accum,
-                             rt_stats* total) {
+                             uint64_t seed, uint32_t flags, int device, bool device_rays,
+                             std::vector<float>& accum, rt_stats* total) {
   const int W = cam.image_width, H = cam.image_height, S = cam.sqrt_spp;
   rth_projection pr;
   std::memset(&pr, 0, sizeof(pr));
@@ -313,11 +404,53 @@ static int render_projection(const rt_scene_blob& blob, const rt_camera& cam, in
   rp.max_depth = cam.max_depth;
   rp.stream_skip = 3;  // the generator's two jitter draws and its time draw
   for (int k = 0; k < 3; ++k) rp.background[k] = cam.background[k];
-  std::vector<rt_ray> rays((size_t)W * H);  // operator new: 16-byte aligned
+  const size_t n_rays = (size_t)W * H;
+  std::vector<rt_ray> rays(device_rays ? 0 : n_rays);  // operator new: 16-byte aligned
+  DeviceBuffer d_rays, d_accum;
+  rt_projection dpr;  // the layout of rth_projection
+  static_assert(sizeof(dpr) == sizeof(pr), "rt_projection mirrors rth_projection");
+  std::memcpy(&dpr, &pr, sizeof(dpr));
   rt_scene* sc = nullptr;
+  rt_raygen* rg = nullptr;
   int rc = rt_scene_create(&blob, device, &sc);
   std::memset(total, 0, sizeof(*total));
-  for (int s_j = 0; rc == RT_OK && s_j < S; ++s_j)
+  if (rc == RT_OK && device_rays) {
+    if (!d_rays.alloc(device, n_rays * sizeof(rt_ray)) ||
+        !d_accum.alloc(device, accum.size() * sizeof(float))) {
+      std::fprintf(stderr, "--device-rays: device buffers: %s\n",
+                   hipGetErrorString(hipGetLastError()));
+      rt_scene_destroy(sc);
+      return 1;
+    }
+    rc = rt_raygen_create(device, &rg);
+  }
+  double ms_gen = 0.0;
+  for (int s_j = 0; rc == RT_OK && device_rays && s_j < S; ++s_j)
+    for (int s_i = 0; rc == RT_OK && s_i < S; ++s_i) {
+      rt_stats st_gen, st;
+      rc = rt_projection_rays_device(rg, &dpr, nullptr, seed, s_i, s_j, 0, H, (rt_ray*)d_rays.p,
+                                     nullptr, &st_gen);
+      if (rc != RT_OK) break;
+      rp.flags = (flags & ~RT_FLAG_OVERWRITE) | (s_i + s_j == 0 ? RT_FLAG_OVERWRITE : 0u);
+      rc = rt_render_rays_device(sc, &rp, (const rt_ray*)d_rays.p, n_rays, (float*)d_accum.p,
+                                 nullptr, &st);
+      ms_gen += st_gen.ms_kernel;
+      total->ms_kernel += st.ms_kernel;
+      total->samples += st.samples;
+      total->launches += st.launches;
+    }
+  if (device_rays) {
+    rt_raygen_destroy(rg);
+    if (rc == RT_OK && hipMemcpy(accum.data(), d_accum.p, accum.size() * sizeof(float),
+                                 hipMemcpyDeviceToHost) != hipSuccess) {
+      std::fprintf(stderr, "--device-rays: download: %s\n", hipGetErrorString(hipGetLastError()));
+      rt_scene_destroy(sc);
+      return 1;
+    }
+    if (rc == RT_OK)
+      std::fprintf(stderr, "rays formed on the device: %.3f ms in %d kernels\n", ms_gen, S * S);
+  }
+  for (int s_j = 0; rc == RT_OK && !device_rays && s_j < S; ++s_j)
     for (int s_i = 0; rc == RT_OK && s_i < S; ++s_i) {
       if (rth_projection_rays(&pr, nullptr, seed, s_i, s_j, rays.data()) != 0) {
         std::fprintf(stderr, "projection: %s\n", rth_last_error());
@@ -333,7 +466,8 @@ static int render_projection(const rt_scene_blob& blob, const rt_camera& cam, in
     }
   rt_scene_destroy(sc);
   if (rc != RT_OK) {
-    std::fprintf(stderr, "rt_render_rays: %d %s\n", rc, rt_last_error());
+    std::fprintf(stderr, "rt_render_rays%s: %d %s\n", device_rays ? " --device-rays" : "", rc,
+                 rt_last_error());
     return 1;
   }
   for (float& v : accum)
@@ -361,6 +495,7 @@ int main(int argc, char** argv) {
   bool pick = false;  // one ray query through pixel (pick_x, pick_y) instead of a render
   int pick_x = 0, pick_y = 0;
   int projection = RTH_PROJ_PINHOLE;  // another one: the frame through rt_render_rays
+  bool device_rays = false;  // --ao and --projection form their rays on the GPU
   double fov = 0.0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -430,6 +565,7 @@ int main(int argc, char** argv) {
         return 2;
       }
     } else if (a == "--ao-radius") ao_radius = std::atof(next());
+    else if (a == "--device-rays") device_rays = true;
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -461,6 +597,11 @@ int main(int argc, char** argv) {
                  "--projection, --device-output or --auto-exposure: it renders no radiance\n");
     return 2;
   }
+  if (device_rays && !ao_k && projection == RTH_PROJ_PINHOLE) {
+    std::fprintf(stderr,
+                 "--device-rays needs --ao or --projection: the other modes take no caller rays\n");
+    return 2;
+  }
   if (ao_k && !(ao_radius > 1e-4)) {
     std::fprintf(stderr, "--ao-radius R: R > 1e-4\n");
     return 2;
@@ -484,7 +625,8 @@ int main(int argc, char** argv) {
     return status;
   }
   if (ao_k) {
-    const int status = render_ao(blob, cam, ao_k, ao_radius, seed, device, out);
+    const int status = device_rays ? render_ao_device(blob, cam, ao_k, ao_radius, seed, device, out)
+                                   : render_ao(blob, cam, ao_k, ao_radius, seed, device, out);
     rth_scene_free(s);
     return status;
   }
@@ -516,7 +658,8 @@ int main(int argc, char** argv) {
   rt_stats st;
   int rc;
   if (projection != RTH_PROJ_PINHOLE) {
-    if (render_projection(blob, cam, projection, fov, seed, o.flags, device, accum, &st) != 0)
+    if (render_projection(blob, cam, projection, fov, seed, o.flags, device, device_rays, accum,
+                          &st) != 0)
       return 1;
   } else if (adaptive) {
     // the adaptive driver; with --denoise the plain filter over its resolved frame

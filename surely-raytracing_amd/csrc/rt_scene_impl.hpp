@@ -5,9 +5,10 @@
 // rt_rays.hip (the tile-list and ray instances of the path kernels), rt_aov.hip (the first-hit AOV
 // pass) and rt_query.hip (the ray queries). The two passes on the interpreter's plan string these
 // steps together in rt_pass.hpp. The stage handles' translation units (rt_denoise.hip,
-// rt_temporal.hip, rt_adaptive.hip, rt_output.hip) know nothing of scenes and take only set_err,
-// HIP_TRY and RT_TRY from here, through rt_stage.hpp, which holds the handle lifecycle and the
-// host-buffer staging of every pass. Internal: nothing here is part of the C ABI.
+// rt_temporal.hip, rt_adaptive.hip, rt_output.hip; rt_raygen.hip, whose driver also reads a
+// scene's device ordinal) know nothing of scenes and take only set_err, HIP_TRY and RT_TRY from
+// here, through rt_stage.hpp, which holds the handle lifecycle and the host-buffer staging of
+// every pass. Internal: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,8 @@
-// rt_stage.hpp — what the stage handles (rt_denoiser, rt_temporal, rt_adaptive, rt_output_stage)
-// share, and the host-buffer path of every pass: the handle's fields, creation and destruction,
-// the workspace growth, the run guard that orders a handle's calls, the stats read-back
-// (rts::Stage, rts::Run), one device allocation made of parts with its uploads and downloads
-// (rts::Staging), and the calls' clock (rts::ms_since). Host only; DESIGN.md §4.2c.
+// rt_stage.hpp — what the stage handles (rt_denoiser, rt_temporal, rt_adaptive, rt_output_stage,
+// rt_raygen) share, and the host-buffer path of every pass: the handle's fields, creation and
+// destruction, the workspace growth, the run guard that orders a handle's calls, the stats
+// read-back (rts::Stage, rts::Run), one device allocation made of parts with its uploads and
+// downloads (rts::Staging), and the calls' clock (rts::ms_since). Host only; DESIGN.md §4.2c.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -172,11 +172,30 @@ class RthProjection(C.Structure):
                 ("forward", C.c_double * 3), ("up", C.c_double * 3), ("fov", C.c_double)]
 
 
+class RtProjection(C.Structure):  # the layout of RthProjection
+    _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("sqrt_spp", C.c_int32), ("origin", C.c_double * 3),
+                ("forward", C.c_double * 3), ("up", C.c_double * 3), ("fov", C.c_double)]
+
+
+class RtAoParams(C.Structure):  # the layout of RthAoParams
+    _fields_ = [("seed", C.c_uint64), ("radius", C.c_double), ("tmin", C.c_double),
+                ("dir_index", C.c_uint32), ("_pad0", C.c_uint32)]
+
+
+class RtAoFrameParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("radius", C.c_double), ("tmin", C.c_double),
+                ("directions", C.c_uint32), ("flags", C.c_uint32), ("channels", C.c_uint32),
+                ("chunk_rays", C.c_uint32)]
+
+
 # ray renders (rt_render_rays*)
 RT_RAYS_STREAM_TIME = 0x1  # a path's time is the last skipped draw, not ray.time
 RT_RAYS_MAX_SKIP = 16
 # host ray generator (rt_host.h rth_projection_rays)
 RTH_PROJ_PINHOLE, RTH_PROJ_ORTHO, RTH_PROJ_PANORAMA, RTH_PROJ_FISHEYE = 0, 1, 2, 3
+# device ray generator (rt_projection_rays_device): the same values
+RT_PROJ_PINHOLE, RT_PROJ_ORTHO, RT_PROJ_PANORAMA, RT_PROJ_FISHEYE = 0, 1, 2, 3
 PROJECTIONS = {"pinhole": RTH_PROJ_PINHOLE, "ortho": RTH_PROJ_ORTHO,
                "panorama": RTH_PROJ_PANORAMA, "fisheye": RTH_PROJ_FISHEYE}
 
@@ -459,6 +478,19 @@ def load_device_lib(path: Path) -> C.CDLL:
                                             C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
         "rt_render_rays": (C.c_int, [p, C.POINTER(RtRaysParams), C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.POINTER(RtStats)]),
+        "rt_raygen_create": (C.c_int, [C.c_int, C.POINTER(p)]),
+        "rt_raygen_destroy": (None, [p]),
+        "rt_projection_rays_device": (C.c_int, [p, C.POINTER(RtProjection), C.POINTER(RtCamera),
+                                                C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.POINTER(RtStats)]),
+        "rt_ao_rays_device": (C.c_int, [p, C.POINTER(RtAoParams), C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_ao_accumulate_device": (C.c_int, [p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.POINTER(RtStats)]),
+        "rt_ambient_occlusion_device": (C.c_int, [p, p, C.POINTER(RtAoFrameParams), C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(RtStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1371,6 +1403,157 @@ class Output:
         if stats:
             res += (st,)
         return None if not res else res[0] if len(res) == 1 else res
+
+
+# ---------------------------------------------------------------------------- ray generators
+def make_projection(kind, width: int = 0, height: int = 0, sqrt_spp: int = 1,
+                    origin=(0.0, 0.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0),
+                    fov: float = 0.0) -> RtProjection:
+    """rt_projection (the fields of projection_rays above). kind: a PROJECTIONS name or value."""
+    pr = RtProjection()
+    pr.kind = PROJECTIONS[kind] if isinstance(kind, str) else int(kind)
+    pr.width, pr.height, pr.sqrt_spp, pr.fov = width, height, sqrt_spp, fov
+    pr.origin, pr.forward, pr.up = _d3(origin), _d3(forward), _d3(up)
+    return pr
+
+
+def make_ao_frame_params(directions: int, seed: int = 1, radius: float = float("inf"),
+                         tmin: float = 1e-4, flags: int = RT_FLAG_OVERWRITE, channels: int = 3,
+                         chunk_rays: int = 0) -> RtAoFrameParams:
+    """rt_ao_frame_params: K directions per ray over [tmin, radius]; flags: RT_FLAG_OVERWRITE
+    and RT_FLAG_REFERENCE_BVH; chunk_rays 0 = the default chunk."""
+    return RtAoFrameParams(seed, radius, tmin, directions, flags, channels, chunk_rays)
+
+
+_hip_rt = None
+
+
+def _hip() -> C.CDLL:
+    """The HIP runtime the device library links, for RayGen.ambient_occlusion's staging."""
+    global _hip_rt
+    if _hip_rt is None:
+        device_lib()  # loads libamdhip64.so.7 as a dependency
+        h = C.CDLL("libamdhip64.so.7")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipFree.argtypes = [C.c_void_p]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipSetDevice.argtypes = [C.c_int]
+        _hip_rt = h
+    return _hip_rt
+
+
+class RayGen:
+    """The ray generators on one GPU (rt_raygen_create): projection rays, ambient-occlusion ray
+    batches and the count of unoccluded directions formed in device buffers, and the AO frame
+    driver over DeviceScene's queries. projection_rays and ao_rays above stay the host reference.
+    Calls on one RayGen are serialised and ordered."""
+
+    def __init__(self, device: int = 0):
+        self._lib = device_lib()
+        self.device = device
+        h = C.c_void_p()
+        _check_dev(self._lib.rt_raygen_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rt_raygen_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def projection_rays_device(self, proj: RtProjection, rays_ptr: int, seed: int = 1,
+                               s_i: int = 0, s_j: int = 0, row_begin: int = 0,
+                               n_rows: int | None = None, cam: "RtCamera | None" = None,
+                               stream: int = 0, stats: bool = False):
+        """Asynchronous rt_projection_rays_device: the rays of rows [row_begin, row_begin + n_rows)
+        (default: to the last row) of stratum (s_i, s_j) into n_rows * width rt_ray records at
+        rays_ptr (16-byte aligned). cam: the camera of a "pinhole" projection."""
+        if n_rows is None:
+            pin = proj.kind == RT_PROJ_PINHOLE and cam is not None
+            n_rows = (cam.image_height if pin else proj.height) - row_begin
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_projection_rays_device(
+            self._h, C.byref(proj), C.byref(cam) if cam is not None else None, seed, s_i, s_j,
+            row_begin, n_rows, C.c_void_p(rays_ptr), C.c_void_p(stream or None),
+            C.byref(st) if st is not None else None))
+        return st
+
+    def ao_rays_device(self, primary_ptr: int, hits_ptr: int, n: int, out_ptr: int, k: int,
+                       seed: int = 1, radius: float = float("inf"), tmin: float = 1e-4,
+                       stream: int = 0, stats: bool = False):
+        """Asynchronous rt_ao_rays_device: the k-th AO batch of n primary rays and their records
+        into n rt_ray records at out_ptr (which may be primary_ptr)."""
+        ap = RtAoParams(seed, radius, tmin, k, 0)
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_ao_rays_device(
+            self._h, C.byref(ap), C.c_void_p(primary_ptr), C.c_void_p(hits_ptr), n,
+            C.c_void_p(out_ptr), C.c_void_p(stream or None),
+            C.byref(st) if st is not None else None))
+        return st
+
+    def ao_accumulate_device(self, occ_ptr: int, n: int, sums_ptr: int, channels: int = 3,
+                             flags: int = 0, stream: int = 0, stats: bool = False):
+        """Asynchronous rt_ao_accumulate_device: every 0 byte of the n at occ_ptr adds 1 to the
+        `channels` floats of its ray at sums_ptr (RT_FLAG_OVERWRITE: replaces them)."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_ao_accumulate_device(
+            self._h, C.c_void_p(occ_ptr), n, channels, flags, C.c_void_p(sums_ptr),
+            C.c_void_p(stream or None), C.byref(st) if st is not None else None))
+        return st
+
+    def ambient_occlusion_device(self, scene: "DeviceScene", params: RtAoFrameParams,
+                                 primary_ptr: int, n: int, sums_ptr: int, hits_ptr: int = 0,
+                                 stream: int = 0, stats: bool = False):
+        """Asynchronous rt_ambient_occlusion_device: per ray the number of unoccluded directions
+        of params.directions, params.channels floats per ray at sums_ptr; the primaries' records
+        at hits_ptr if it is given."""
+        st = RtStats() if stats else None
+        _check_dev(self._lib.rt_ambient_occlusion_device(
+            self._h, scene._h, C.byref(params), C.c_void_p(primary_ptr), n, C.c_void_p(sums_ptr),
+            C.c_void_p(hits_ptr or None), C.c_void_p(stream or None),
+            C.byref(st) if st is not None else None))
+        return st
+
+    def ambient_occlusion(self, scene: "DeviceScene", rays: np.ndarray, K: int, seed: int = 1,
+                          radius: float = float("inf"), tmin: float = 1e-4, flags: int = 0,
+                          channels: int = 1, chunk_rays: int = 0, want_hits: bool = False,
+                          stats: bool = False):
+        """Synchronous, host buffers: the AO frame of a RAY_DTYPE array, staged through device
+        memory. Returns float32 [n, channels] counts of unoccluded directions out of K (a ray
+        that sees no surface: 0); with want_hits also the HIT_DTYPE records, with stats RtStats."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        n = len(rays)
+        sums = np.zeros((n, channels), np.float32)
+        hits = np.zeros(n if want_hits else 0, HIT_DTYPE)
+        st = RtStats()
+        if n:
+            params = make_ao_frame_params(K, seed, radius, tmin, flags | RT_FLAG_OVERWRITE,
+                                          channels, chunk_rays)
+            h = _hip()
+            if h.hipSetDevice(self.device) != 0:
+                raise RtError(RT_ERR_HIP, "hipSetDevice failed")
+            sizes = [rays.nbytes, sums.nbytes, hits.nbytes]
+            offs = [0, (sizes[0] + 255) & ~255]
+            offs.append(offs[1] + ((sizes[1] + 255) & ~255))
+            base = C.c_void_p()
+            if h.hipMalloc(C.byref(base), offs[2] + max(sizes[2], 256)) != 0:
+                raise RtError(RT_ERR_HIP, "hipMalloc of the staging buffer failed")
+            try:
+                d_rays, d_sums, d_hits = (base.value + o for o in offs)
+                if h.hipMemcpy(C.c_void_p(d_rays), rays.ctypes.data, sizes[0], 1) != 0:
+                    raise RtError(RT_ERR_HIP, "upload of the rays failed")
+                st = self.ambient_occlusion_device(scene, params, d_rays, n, d_sums,
+                                                   d_hits if want_hits else 0, stats=True)
+                if h.hipMemcpy(sums.ctypes.data, C.c_void_p(d_sums), sizes[1], 2) != 0 or (
+                        want_hits and
+                        h.hipMemcpy(hits.ctypes.data, C.c_void_p(d_hits), sizes[2], 2) != 0):
+                    raise RtError(RT_ERR_HIP, "download of the AO frame failed")
+            finally:
+                h.hipFree(base)
+        res = (sums,) + ((hits,) if want_hits else ()) + ((st,) if stats else ())
+        return res[0] if len(res) == 1 else res
 
 
 def write_ppm(path: str, rgb8: np.ndarray) -> None:
